@@ -23,6 +23,11 @@ the batches applied in the timed region / the region's time between HIP events r
 engine's own stream before its first and after its last launch (rmq_profile_*); algorithmic bytes
 per record = (8 + L) read + RF * (16 + L) written, plus RF*8 + 16 per partition
 per batch.
+
+A plain run sets up, warms up, times --steps appends and prints the line. --full adds the side legs
+after the timed steps (host-memory path, fetch, mixed append + fetch, durable tier, CPU baseline);
+their own options (--fetch-rounds, --no-cpu-baseline, ...) apply only with it. --dump-outputs DIR
+writes what the last timed append returned and left behind (dump_outputs) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -642,6 +647,43 @@ def consumer_loop(eng, spec: StreamSpec, pp, cc, hw, lo, g, loops: int, mx: int 
                          "bytes": "B_fetch = 2 (16 + L) per returned record (no index search on a cache hit)"}}
 
 
+DUMP_RINGS = 16  # partitions whose rings --dump-outputs samples
+DUMP_RING_BYTES = 64 << 10  # leading bytes of each sampled ring (RING_FLOOR: every ring of the load policy has them)
+
+
+def dump_outputs(path: str, eng, n: int, d_offsets: int, stats: dict) -> None:
+    """--dump-outputs: what the caller of the last timed rmq_append received and what the timed path
+    left in the engine, as .npy files under `path` (float64, the ring bytes float32; offsets and
+    positions are far below 2^53, so the conversion is exact):
+      offsets                 the n log offsets written for the last batch's records
+      append_stats            the batch's rmq_append_stats fields in declaration order
+      partition_states        rmq_get_partition_states of every partition, a row each, fields in
+                              declaration order (match, replica_rank: RMQ_MAX_RF columns each)
+      ring_sample_partitions  the busiest partition and DUMP_RINGS - 1 more drawn with a fixed seed
+      ring_sample             the first DUMP_RING_BYTES of every replica ring of those partitions,
+                              [partition, replica, byte]
+    The inputs are seeded (workload.make_batch), so the same arguments give the same files."""
+    os.makedirs(path, exist_ok=True)
+    off = np.empty(n, np.uint64)
+    eng.d2h(off, d_offsets)
+    np.save(os.path.join(path, "offsets.npy"), off.astype(np.float64))
+    np.save(os.path.join(path, "append_stats.npy"), np.array(list(stats.values()), np.float64))
+    st = eng.states()
+    np.save(os.path.join(path, "partition_states.npy"),
+            np.hstack([np.asarray(st[f], np.float64).reshape(len(st), -1) for f in st.dtype.names]))
+    P, rf = len(st), eng.cfg.replication_factor
+    hot = int(np.argmax(st["log_end_offset"]))
+    rest = np.random.default_rng(0x5249504F).permutation(P)
+    parts = np.concatenate(([hot], np.sort(rest[rest != hot][:DUMP_RINGS - 1]))).astype(np.int64)
+    nb = int(min(DUMP_RING_BYTES, st["segment_bytes"][parts].min()))
+    rings = np.empty((len(parts), rf, nb), np.float32)
+    for i, p in enumerate(parts.tolist()):
+        for r in range(rf):
+            rings[i, r] = eng.read_segment(r, p, 0, nb)
+    np.save(os.path.join(path, "ring_sample_partitions.npy"), parts.astype(np.float64))
+    np.save(os.path.join(path, "ring_sample.npy"), rings)
+
+
 class SoloGroup:
     """One rank: the identity group."""
     world = 1
@@ -807,6 +849,9 @@ def run_rank(args, grp, device: int, attach) -> dict | None:
     if committed != spec.records * (args.warmup + args.steps) and not timing_only:
         raise SystemExit(f"bench: {committed} records committed of {spec.records * (args.warmup + args.steps)} "
                          "appended; the measurement would be void")
+    if args.dump_outputs:  # every rank (its own engine's view); rank 0 into the folder itself
+        dump_outputs(args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, f"rank{rank}"), eng,
+                     spec.records, d_out[(args.warmup + args.steps - 1) % len(d_out)], st or {})
 
     t_max = grp.max(elapsed)
     sent_max = grp.max(float(x1["bytes_sent"] - x0["bytes_sent"]))
@@ -943,7 +988,16 @@ def main() -> None:
     ap.add_argument("--transport", default="rccl", choices=["rccl", "local"],
                     help="local: --gpus ranks as threads on ONE GPU over the in-process transport "
                          "(functional rehearsal of the multi-GPU path; never a scaling number)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side legs: host-memory path, fetch, mixed append + "
+                         "fetch, durable tier (1 GPU) and the CPU baseline; without it their options are ignored")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned and left in the engine as DIR/<name>.npy "
+                         "(dump_outputs; ranks above 0 into DIR/rank<r>)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, the timed steps, the line
+        args.no_cpu_baseline = True
+        args.host_steps = args.fetch_rounds = args.concurrent_rounds = args.tier_rounds = 0
 
     if args.transport == "local":
         from ripplemq_amd.engine import LocalHub

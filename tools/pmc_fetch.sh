@@ -3,7 +3,7 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"; R=$GRAFT_REPO_ROOT; export HSA_ENABLE_IPC_MODE_LEGACY=0
 T=$1
-Q="--steps 20 --warmup 5 --fetch-rounds 10 --concurrent-rounds 0 --tier-rounds 0 --no-cpu-baseline --host-steps 0"
+Q="--full --steps 20 --warmup 5 --fetch-rounds 10 --concurrent-rounds 0 --tier-rounds 0 --no-cpu-baseline --host-steps 0"
 for c in FETCH_SIZE WRITE_SIZE; do
   (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 150 rocprofv3 --pmc $c -f csv -d "$R/gpurun_out/${T}_$c" -o p -- python3 "$R/bench.py" $Q) > "$R/gpurun_out/${T}_$c.log" 2>&1 || { echo "FAILED $c"; tail -20 "$R/gpurun_out/${T}_$c.log"; exit 1; }
 done

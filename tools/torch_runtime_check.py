@@ -12,6 +12,6 @@ import __graft_entry__ as g  # noqa: E402
 
 g.smoke()
 print("smoke under torch's HIP runtime: ok", flush=True)
-sys.argv = ["bench.py", "--steps", "200", "--warmup", "20", "--no-cpu-baseline", "--fetch-rounds", "2",
+sys.argv = ["bench.py", "--full", "--steps", "200", "--warmup", "20", "--no-cpu-baseline", "--fetch-rounds", "2",
             "--concurrent-rounds", "0", "--host-steps", "0", "--tier-rounds", "0"]
 runpy.run_path("bench.py", run_name="__main__")
