@@ -68,7 +68,7 @@
 extern "C" {
 #endif
 
-#define RMQ_ABI_VERSION 10u
+#define RMQ_ABI_VERSION 11u
 #define RMQ_MAX_RF 8u
 #define RMQ_ALL_PARTITIONS 0xFFFFFFFFu
 #define RMQ_OFFSET_NONE 0xFFFFFFFFFFFFFFFFull /* out_offsets value of a rejected record */
@@ -89,8 +89,10 @@ enum {
   RMQ_ENOMEM = -7,
   RMQ_ESTALE = -8,     /* rmq_become_leader: this replica lacks records its partition's leader
                           committed (Raft's vote restriction: it may not lead) */
-  RMQ_ETERM = -9       /* rmq_become_leader: the term already has a leader here (this replica led it,
+  RMQ_ETERM = -9,      /* rmq_become_leader: the term already has a leader here (this replica led it,
                           or voted for another candidate in it: Raft's one vote per term) */
+  RMQ_ECORRUPT = -10   /* ABI 11: a stored record fails its CRC32C or the log's structure (FORMAT.md §10):
+                          rmq_scrub, and a fetch request with RMQ_FETCH_VERIFY */
 };
 #define RMQ_NO_VOTE 0xFFFFFFFFu /* rmq_partition_state.voted_for: no vote in voted_term */
 
@@ -137,7 +139,7 @@ typedef struct rmq_fetch_req {
   uint32_t pidx;
   uint32_t consumer;           /* dense consumer id in [0, max_consumers) */
   uint32_t max_records;        /* reference: MessageBatchReadRequest.maxMessages */
-  uint32_t flags;              /* RMQ_FETCH_COMMIT, or 0 */
+  uint32_t flags;              /* RMQ_FETCH_COMMIT | RMQ_FETCH_REPLICA | RMQ_FETCH_VERIFY, or 0 */
 } rmq_fetch_req;
 /* rmq_fetch_req.flags: once the request is served (RMQ_OK, its records in the output) or answered
    RMQ_EOFFSET, commit the consumer's next offset — start_offset + count (the first retained offset
@@ -155,6 +157,17 @@ typedef struct rmq_fetch_req {
    replica's durable tier reads its own log: jraft keeps the whole log on every node
    (PartitionRaftServer.java:53,88-90), so a follower persists what it holds, not only a leader. */
 #define RMQ_FETCH_REPLICA 2u
+/* rmq_fetch_req.flags (ABI 11): once the request's slice is in the output, check every record of
+   it as FORMAT.md §1 prescribes (header offsets start_offset, start_offset + 1, ..., records back to
+   back filling `bytes` exactly, CRC32C of the payload, zero padding). A slice with a failing record
+   is answered status RMQ_ECORRUPT and count 0; its start_offset, out_pos and bytes stay, so the
+   caller sees what was refused and the out_pos of later requests do not move (a host output keeps
+   its bytes of that range as they were). rmq_fetch / rmq_fetch_poll still return RMQ_OK or
+   RMQ_ENOSPC: corruption is reported per request. With RMQ_FETCH_COMMIT a refused request commits
+   nothing. Valid with RMQ_FETCH_REPLICA. Host rows only (device rows: flags 0, ignored). A call
+   with such a request is never held back to go with later asynchronous fetches. (Bits 4, 8 and 16
+   stay unknown flags, refused with RMQ_EINVAL as before.) */
+#define RMQ_FETCH_VERIFY 0x20u
 
 typedef struct rmq_fetch_res {
   uint64_t start_offset;       /* reference: MessageBatchReadResponse.offset (the consumer offset);
@@ -162,7 +175,8 @@ typedef struct rmq_fetch_res {
   uint64_t out_pos;            /* byte position of this request's records in the output buffer */
   uint32_t count;              /* records returned (reference: messages.size()) */
   uint32_t bytes;              /* bytes of the returned records (FORMAT.md record layout) */
-  int32_t status;              /* RMQ_OK, RMQ_ENOTLEADER, RMQ_ENOPART, RMQ_EINVAL, RMQ_EOFFSET, RMQ_ENOSPC */
+  int32_t status;              /* RMQ_OK, RMQ_ENOTLEADER, RMQ_ENOPART, RMQ_EINVAL, RMQ_EOFFSET, RMQ_ENOSPC,
+                                  RMQ_ECORRUPT (RMQ_FETCH_VERIFY) */
   uint32_t reserved;
 } rmq_fetch_res;
 
@@ -419,6 +433,33 @@ int rmq_read_consumer_offsets(rmq_engine* e, uint32_t pidx, uint64_t* out /* max
 /* The consumer-offset rows of partitions [first, first + n): out[n][max_consumers]. */
 int rmq_read_consumer_table(rmq_engine* e, uint32_t first, uint32_t n, uint64_t* out);
 
+/* ---- scrub (ABI 11, FORMAT.md §10) ---- */
+#define RMQ_SCRUB_BAD_CRC   1u  /* CRC32C of the payload differs from the header's, or a padding byte is not zero */
+#define RMQ_SCRUB_BAD_CHAIN 2u  /* header offset is not the expected one, the record runs past its segment's end,
+                                   or the walk from an index entry does not land on the next entry / the log end */
+typedef struct rmq_scrub_res {
+  uint64_t records_ok;   /* records that passed, summed over the local replicas checked */
+  uint64_t bytes_ok;     /* their record bytes (16 + align16(len)) */
+  uint64_t bad_offset;   /* lowest expected offset of a failing record; RMQ_OFFSET_NONE if none */
+  uint32_t bad_replica;  /* lowest replica slot on which that offset fails */
+  uint32_t bad_kind;     /* RMQ_SCRUB_BAD_* of that (offset, replica) */
+  uint32_t replicas;     /* local replica slots checked (0: this engine holds no replica of the partition) */
+  int32_t status;        /* RMQ_OK or RMQ_ECORRUPT */
+} rmq_scrub_res;
+/* On-device audit of the retained logs [log_start_offset, log_end_offset) of every local replica
+   slot of partitions [first, first + n), led or followed: every record's header offset, extent,
+   CRC32C and zero padding, and the sparse index entries that tile the log (FORMAT.md §10). res
+   (host, [n], nullable) gets one row per partition. Returns RMQ_OK if every partition is clean,
+   RMQ_ECORRUPT if any is not (the rows say where), RMQ_ENOPART if the range leaves [0, P). Changes no
+   engine state. Drains first, like rmq_sync: with a transport attached the call is collective (every
+   rank makes it at the same point of its call sequence). */
+int rmq_scrub(rmq_engine* e, uint32_t first, uint32_t n, rmq_scrub_res* res);
+/* Fault injection (tests): XORs the byte at ring_off of replica slot `replica`'s ring of pidx
+   (addressed as rmq_read_segment addresses it) with the low 8 bits of xor_mask, as a memory
+   corruption would. RMQ_EINVAL for a slot this engine does not hold, ring_off >= the ring's bytes
+   or a zero mask. Drains first (collective with a transport, like rmq_sync). */
+int rmq_fault_flip_ring(rmq_engine* e, uint32_t replica, uint32_t pidx, uint64_t ring_off, uint32_t xor_mask);
+
 /* ---- host utilities ---- */
 /* FORMAT.md §1 records laid back to back in host memory (segment files of a durable tier, fetch
    output): walks them from buf[0], expecting header offsets first, first + 1, ..., and stops at the
@@ -459,7 +500,9 @@ int rmq_host_unregister(rmq_engine* e, void* p);
    outside), launches = kernel executions. enable = k >= 2 also runs every fetch's kernels k times
    back to back (idempotent: the same results), so kernel 4 / launches is a kernel time that no
    copy or host gap inflates and a rocprofv3 trace shows the kernels back to back; a fetch with an
-   RMQ_FETCH_COMMIT request runs once (each run would commit). 2: unused. */
+   RMQ_FETCH_COMMIT or RMQ_FETCH_VERIFY request runs once (each run would commit; the verify
+   rewrites the rows). 2: rmq_scrub, an event before its first kernel (the plan) to one after its last
+   (the verify), launches = calls. */
 int rmq_profile_enable(rmq_engine* e, int enable);
 int rmq_profile_query(rmq_engine* e, int kernel, uint64_t* launches, double* total_ms);
 /* Device name / CU count for reports. */

@@ -15,9 +15,10 @@ REPO = os.path.dirname(HERE)
 HEADER = os.path.join(REPO, "include", "ripplemq_engine.h")
 LIB_PATH = os.environ.get("RMQ_LIB") or os.path.join(HERE, "libripplemq_engine.so")
 
-RMQ_ABI_VERSION = 10
+RMQ_ABI_VERSION = 11
 RMQ_FETCH_COMMIT = 1
 RMQ_FETCH_REPLICA = 2
+RMQ_FETCH_VERIFY = 0x20
 RMQ_FETCH_PINNED_ROWS = 0x100
 RMQ_FETCH_DEVICE_ROWS = 0x200
 RMQ_MAX_RF = 8
@@ -26,6 +27,8 @@ RMQ_OFFSET_NONE = 0xFFFFFFFFFFFFFFFF
 RMQ_RECORD_HEADER_BYTES = 16
 RMQ_TICKET_OFFSETS = 1 << 63
 RMQ_SCAN_CHECK = 1
+RMQ_SCRUB_BAD_CRC = 1
+RMQ_SCRUB_BAD_CHAIN = 2
 
 RMQ_OK = 0
 RMQ_PENDING = 1
@@ -38,6 +41,7 @@ RMQ_EOFFSET = -6
 RMQ_ENOMEM = -7
 RMQ_ESTALE = -8
 RMQ_ETERM = -9
+RMQ_ECORRUPT = -10
 RMQ_NO_VOTE = 0xFFFFFFFF
 
 RMQ_MEM_HOST = 0
@@ -48,7 +52,7 @@ STATUS_NAMES = {
     RMQ_OK: "RMQ_OK", RMQ_PENDING: "RMQ_PENDING", RMQ_ENOTLEADER: "RMQ_ENOTLEADER",
     RMQ_ENOPART: "RMQ_ENOPART", RMQ_EINVAL: "RMQ_EINVAL", RMQ_ENOSPC: "RMQ_ENOSPC",
     RMQ_EDEVICE: "RMQ_EDEVICE", RMQ_EOFFSET: "RMQ_EOFFSET", RMQ_ENOMEM: "RMQ_ENOMEM",
-    RMQ_ESTALE: "RMQ_ESTALE", RMQ_ETERM: "RMQ_ETERM",
+    RMQ_ESTALE: "RMQ_ESTALE", RMQ_ETERM: "RMQ_ETERM", RMQ_ECORRUPT: "RMQ_ECORRUPT",
 }
 
 u32 = C.c_uint32
@@ -100,6 +104,13 @@ class RmqReplStats(C.Structure):
         ("bytes_sent", u64), ("bytes_received", u64), ("records_ingested", u64), ("refused_crc", u64),
         ("refused_log", u64), ("bytes_ingested", u64), ("catchup_entries", u64), ("detached_plans", u64),
         ("general_plans", u64), ("host_waits", u64), ("host_wait_ns", u64),
+    ]
+
+
+class RmqScrubRes(C.Structure):
+    _fields_ = [
+        ("records_ok", u64), ("bytes_ok", u64), ("bad_offset", u64), ("bad_replica", u32),
+        ("bad_kind", u32), ("replicas", u32), ("status", i32),
     ]
 
 
@@ -166,6 +177,8 @@ _SIGS = {
     "rmq_fault_corrupt": (C.c_int, [vp, u32, C.c_int64]),
     "rmq_fault_isolate": (C.c_int, [vp, u32, u32]),
     "rmq_fault_cut": (C.c_int, [vp, u32, u32]),
+    "rmq_scrub": (C.c_int, [vp, u32, u32, vp]),
+    "rmq_fault_flip_ring": (C.c_int, [vp, u32, u32, u64, u32]),
     "rmq_scan_records": (C.c_int, [vp, u64, u64, u64, u32, vp, C.POINTER(u64), C.POINTER(u64)]),
     "rmq_tier_append": (C.c_int, [u32, vp, vp, vp, vp, vp, vp, vp, u32, C.c_int]),
 }

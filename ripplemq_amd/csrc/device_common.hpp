@@ -198,6 +198,63 @@ __device__ __forceinline__ u32 wave_xor_all(u32 v) {
   return (u32)__builtin_amdgcn_readlane((int)v, 63);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Record checks shared by the scrub and the verified fetch (FORMAT.md §10)
+// ---------------------------------------------------------------------------------------------
+
+// Whether the bytes of a record's last 16-byte piece past its payload (L bytes) are zero.
+__device__ __forceinline__ bool pad_zero16(const uint4 t, u32 L) {
+  const u32 nb = L & 15u;  // payload bytes in the last piece (0: it is all payload)
+  u32 z = 0;
+  const u32 w4[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+  for (u32 i = 0; i < 4; ++i) {
+    const u32 lo = 4u * i;  // the word's first byte
+    const u32 keep = nb <= lo ? 0u : nb >= lo + 4u ? 0xFFFFFFFFu : (1u << (8u * (nb - lo))) - 1u;
+    z |= w4[i] & ~keep;
+  }
+  return nb == 0u || z == 0u;
+}
+
+// The CRC32C register (from ~0) over the m16 payload pieces of ONE record by the whole wave (m16
+// wave-uniform, every lane calls): lane l takes pieces l, l + 64, ... (Horner with the 1 KB shift
+// read from global memory), shifts past the pieces after its last one, and the lanes' registers
+// are XORed; piece(j) loads piece j < m16. t8: the slicing tables in LDS.
+template <typename F>
+__device__ __forceinline__ u32 wave_crc_pieces(const CrcConsts* crc, const u32 (*t8)[256], u32 m16, F piece) {
+  const u32 lane = lane_id();
+  u32 acc = 0;
+  for (u32 k0 = 0; 64u * k0 < m16; k0 += 4u) {
+    uint4 v[4];
+#pragma unroll
+    for (u32 u = 0; u < 4u; ++u) {  // four pieces in flight per lane
+      const u32 jp = 64u * (k0 + u) + lane;
+      v[u] = jp < m16 ? piece(jp) : make_uint4(0, 0, 0, 0);
+    }
+#pragma unroll
+    for (u32 u = 0; u < 4u; ++u) {
+      const u32 jp = 64u * (k0 + u) + lane;
+      if (jp < m16) {
+        uint4 w = v[u];
+        if (jp == 0) w.x ^= 0xFFFFFFFFu;
+        acc = crc_zshift(crc->zshift1k, acc) ^ crc_piece16(t8, w);
+      }
+    }
+  }
+  if (lane < m16) {
+    const u32 eb = (m16 - 1u - lane) & 63u;
+    if (eb) acc = gf2_mulmod(acc, crc->sh16[eb]);
+  }
+  return wave_xor_all(acc);
+}
+
+// A record's CRC32C from the register over its m16 zero-padded pieces (L payload bytes).
+__device__ __forceinline__ u32 crc_of_padded(const CrcConsts* crc, u32 acc, u32 L, u32 m16) {
+  if (!L) return 0u;
+  const u32 pad = 16u * m16 - L;
+  return ~(pad ? gf2_mulmod(crc->inv_pad[pad], acc) : acc);
+}
+
 // Segmented inclusive scan of pairs (flag, value), a set flag starting a new segment; the same
 // moves, each combining (f, v) with the pair before: v += v' unless f, f |= f'. flag ends as the
 // OR of the flags up to the lane.

@@ -594,7 +594,7 @@ void free_engine(rmq_engine* e) {
   std::vector<void*> bufs = {s.start_off, s.start_pos, s.commit, s.hw, s.term_start, s.term, s.match, s.is_leader,
                              s.local_mask, s.index, s.logs, s.ring, s.cons, s.pcache, s.rcur, s.cdirty, s.lcommit, s.csnap, s.cver, s.cq,
                              s.lterm, s.mterm, s.heard, e->d_crc,
-                             e->d_stats, e->d_ctl32, e->d_ctl64, e->d_stamps, e->d_rlate};
+                             e->d_stats, e->d_ctl32, e->d_ctl64, e->d_stamps, e->d_rlate, e->d_scrub_tbase, e->d_scrub_rows};
   if (e->state_stage) hipHostFree(e->state_stage);
   for (rmq_engine::FetchSlot& f : e->fslot) {
     void* fs[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_out};
@@ -714,6 +714,7 @@ const char* rmq_strerror(int s) {
     case RMQ_ENOMEM: return "out of memory";
     case RMQ_ESTALE: return "replica lags the committed log";
     case RMQ_ETERM: return "term already led or voted for another candidate";
+    case RMQ_ECORRUPT: return "record checksum or log structure is corrupt";
     default: return "unknown status";
   }
 }
@@ -1745,7 +1746,7 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t m
     e->fetch_done.push_back({old, (uint64_t)(int64_t)rc, used});
   }
   // RMQ_FETCH_COMMIT: known flags only, one committing request per (partition, consumer)
-  bool any = false, replica = false;
+  bool any = false, replica = false, verify = false;
   if (!rows_dev) {  // (device rows: never read here; their flags are ignored)
     // the OR of every row's flags word (the high half of its second 8-byte word), four rows per
     // step with no early exit: 16,384 rows in a few us instead of a branch per row
@@ -1762,9 +1763,10 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t m
     }
     for (; r < n; ++r) a0 |= w[2 * r + 1];
     const uint32_t fl = (uint32_t)((a0 | a1 | a2 | a3) >> 32);
-    if (fl & ~(RMQ_FETCH_COMMIT | RMQ_FETCH_REPLICA)) return RMQ_EINVAL;
+    if (fl & ~(RMQ_FETCH_COMMIT | RMQ_FETCH_REPLICA | RMQ_FETCH_VERIFY)) return RMQ_EINVAL;
     any = (fl & RMQ_FETCH_COMMIT) != 0;
     replica = (fl & RMQ_FETCH_REPLICA) != 0;
+    verify = (fl & RMQ_FETCH_VERIFY) != 0;
     if (any) {
       const size_t slots = (size_t)e->cfg.num_partitions * e->cfg.max_consumers;
       if (e->fetch_stamp.size() != slots) {
@@ -1838,7 +1840,8 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t m
     // an asynchronous fetch that commits nothing waits to go with the next ones (up to kFetchBatch
     // tickets in one resolve + gather pair: the requests of different tickets never depend on one
     // another); anything else launches the held ones first, then itself
-    const bool hold = !sync && !any && !dma && !e->profile && e->fetch_coalesce > 1;
+    // (nor does one with an RMQ_FETCH_VERIFY request: its third kernel follows its own gather)
+    const bool hold = !sync && !any && !verify && !dma && !e->profile && e->fetch_coalesce > 1;
     if (!hold) {
       rc = fetch_flush(e);
       if (rc) return rc;
@@ -1861,7 +1864,8 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t m
     a.out_cap = out_cap;
     a.need_host = f.need_dev;
     a.n = n;
-    a.commits = any ? 1u : 0u;
+    // (a ticket with an RMQ_FETCH_VERIFY request: the verify kernel commits, after its verdicts)
+    a.commits = any && !verify ? 1u : 0u;
     a.replica = replica ? 1u : 0u;
     if (hold) {
       const size_t half = (size_t)f.csum_lines * kCsumStride;
@@ -1879,10 +1883,11 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t m
     hipEvent_t ev[4] = {}, r0 = nullptr, r1 = nullptr;
     // (profiling replays a fetch's kernels back to back; a committing fetch runs once: each run
     // would commit again and the next would read from the committed offset)
-    const uint32_t runs = hold ? 0u : e->profile && !any ? e->fetch_replay : 1u;
+    // (nor is a verifying one replayed: its third kernel rewrites the rows the gather wrote)
+    const uint32_t runs = hold ? 0u : e->profile && !any && !verify ? e->fetch_replay : 1u;
     // (a committing fetch records no dispatch spans: the events the kernels' own dispatches record
     // were measured to hold the second kernel ~10 us behind the first, which its one run would carry)
-    const bool spans = e->profile && !any;
+    const bool spans = e->profile && !any && !verify;
     if (e->profile) {  // kernel 3: the first run's dispatch spans; 4: every run
       if (spans) {
         for (hipEvent_t& x : ev) x = pool_event(e);
@@ -1900,6 +1905,19 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t m
       a.csum_next = f.d_csum + half * (f.csum_par ^ 1u);
       f.csum_par ^= 1u;
       launch_fetch(a, e->main_s, spans && k == 0 ? ev : nullptr);
+      HIP_TRY(hipGetLastError());
+    }
+    if (verify) {  // the flagged slices checked in the output, then the ticket's commits
+      FetchVerifyArgs v{};
+      v.st = e->st;
+      v.req_dev = f.d_req;
+      v.rows = a.res_host;
+      v.out = d_out;
+      v.crc = e->d_crc;
+      v.n = n;
+      v.commits = any ? 1u : 0u;
+      v.replica = a.replica;
+      launch_fetch_verify(v, std::max<uint32_t>(e->cu_count, 1u) * 8u, e->main_s);
       HIP_TRY(hipGetLastError());
     }
     if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
@@ -2117,6 +2135,86 @@ int rmq_read_consumer_table(rmq_engine* e, uint32_t first, uint32_t n, uint64_t*
   if (rc) return rc;
   const size_t C = e->cfg.max_consumers;
   HIP_TRY(hipMemcpy(out, e->st.cons + (size_t)first * C, (size_t)n * C * 8, hipMemcpyDeviceToHost));
+  return RMQ_OK;
+}
+
+int rmq_scrub(rmq_engine* e, uint32_t first, uint32_t n, rmq_scrub_res* res) {
+  if (!e) return RMQ_EINVAL;
+  EngineLock g(e);
+  const uint32_t P = e->cfg.num_partitions;
+  if (first > P || n > P - first) return RMQ_ENOPART;
+  if (!n) return RMQ_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  int rc = drain(e);  // (fetches run on the pipeline stream: the drain waited for them too)
+  if (rc) return rc;
+  if (e->scrub_cap < n) {
+    if (e->d_scrub_tbase) hipFree(e->d_scrub_tbase);
+    if (e->d_scrub_rows) hipFree(e->d_scrub_rows);
+    e->d_scrub_tbase = e->d_scrub_rows = nullptr;
+    e->scrub_cap = 0;
+    rc = dalloc(&e->d_scrub_tbase, (size_t)n + 1);
+    if (!rc) rc = dalloc(&e->d_scrub_rows, (size_t)n * 4);
+    if (rc) return rc;
+    e->scrub_cap = n;
+  }
+  ScrubArgs a{};
+  a.st = e->st;
+  a.crc = e->d_crc;
+  a.tbase = e->d_scrub_tbase;
+  a.rows = e->d_scrub_rows;
+  a.first = first;
+  a.n = n;
+  hipEvent_t r0 = nullptr, r1 = nullptr;
+  if (e->profile) {  // kernel 2: an event before the plan to one after the verify
+    r0 = pool_event(e);
+    r1 = pool_event(e);
+    e->prof[2].push_back({r0, r1});
+    HIP_TRY(hipEventRecord(r0, e->main_s));
+  }
+  // the tasks are counted on the device (the plan), so the verify grid is a fixed few workgroups
+  // per CU whose waves stride over them
+  launch_scrub(a, std::max<uint32_t>(e->cu_count, 1u) * 8u, e->main_s);
+  HIP_TRY(hipGetLastError());
+  if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
+  rc = stream_wait(e->main_s);
+  if (rc) return rc;
+  std::vector<uint64_t> rows((size_t)n * 4);
+  HIP_TRY(hipMemcpy(rows.data(), e->d_scrub_rows, rows.size() * 8, hipMemcpyDeviceToHost));
+  bool corrupt = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t key = rows[4ull * i];
+    corrupt = corrupt || key != kScrubClean;
+    if (!res) continue;
+    rmq_scrub_res& x = res[i];
+    std::memset(&x, 0, sizeof x);
+    x.records_ok = rows[4ull * i + 1];
+    x.bytes_ok = rows[4ull * i + 2];
+    x.replicas = (uint32_t)rows[4ull * i + 3];
+    x.bad_offset = key == kScrubClean ? RMQ_OFFSET_NONE : key >> 5;
+    x.bad_replica = key == kScrubClean ? 0u : (uint32_t)(key >> 2) & 7u;
+    x.bad_kind = key == kScrubClean ? 0u : (uint32_t)key & 3u;
+    x.status = key == kScrubClean ? RMQ_OK : RMQ_ECORRUPT;
+  }
+  return corrupt ? RMQ_ECORRUPT : RMQ_OK;
+}
+
+int rmq_fault_flip_ring(rmq_engine* e, uint32_t replica, uint32_t p, uint64_t ring_off, uint32_t xor_mask) {
+  if (!e) return RMQ_EINVAL;
+  EngineLock g(e);
+  if (p >= e->cfg.num_partitions) return RMQ_ENOPART;
+  const uint32_t RF = e->cfg.replication_factor;
+  const RingRef rg = ring_ref(e->ring[p], e->st.interval_log2, e->st.icap_mul);
+  if (replica >= RF || e->ranks[(size_t)p * RF + replica] != e->cfg.rank || ring_off >= rg.seg || !(xor_mask & 0xFFu))
+    return RMQ_EINVAL;
+  HIP_TRY(hipSetDevice(e->device));
+  int rc = drain(e);
+  if (rc) return rc;
+  // one byte inside the partition's own ring block of a local replica region
+  uint8_t* at = e->st.logs + (uint64_t)replica * e->st.rstride + rg.base + ring_off;
+  uint8_t b = 0;
+  HIP_TRY(hipMemcpy(&b, at, 1, hipMemcpyDeviceToHost));
+  b ^= (uint8_t)(xor_mask & 0xFFu);
+  HIP_TRY(hipMemcpy(at, &b, 1, hipMemcpyHostToDevice));
   return RMQ_OK;
 }
 

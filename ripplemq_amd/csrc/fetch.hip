@@ -27,6 +27,7 @@
 // fetch.
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "device_common.hpp"
@@ -476,6 +477,143 @@ __global__ __launch_bounds__(64 * kFW) void fetch_gather_kernel(FetchKArgs<kMult
     for (; p < pieces; p += 64)
       *reinterpret_cast<uint4*>(out + 16ull * p) = *reinterpret_cast<const uint4*>(ring + ((pos0 + 16ull * p) & mask));
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// RMQ_FETCH_VERIFY (FORMAT.md §10): the third kernel of a ticket with a flagged request
+// ---------------------------------------------------------------------------------------------
+constexpr int kCorrupt = -10;
+constexpr u32 kVT = 256;        // threads per verify workgroup: a wave per request
+constexpr u32 kBigVerify = 64;  // records over this many 16-byte pieces: the whole wave (as the scrub)
+
+// The length words of pieces 64 k .. 64 k + 63 of a slice of nb16 pieces (lane l: piece 64 k + l).
+__device__ __forceinline__ u32 slice_lens(const uint8_t* base, u64 nb16, u64 k, u32 lane) {
+  const u64 piece = 64ull * k + lane;
+  return piece < nb16 ? *reinterpret_cast<const u32*>(base + 16ull * piece + 8ull) : 0u;
+}
+
+// Whether the nb16 pieces at base are `count` FORMAT.md §1 records with header offsets start,
+// start + 1, ..., back to back and filling the slice exactly, each with its CRC32C and zero padding
+// (wave-uniform arguments and result). The record starts come from walking the length words, read
+// cooperatively as windows of 64 pieces (the next window in flight while one is walked); then a
+// lane per record, 64 at a time. Nothing outside the slice is read: a window piece, a header and
+// every payload piece are loaded only at piece indices below nb16, and a record's piece count is
+// clamped by the pieces left after its header before any of them is loaded.
+__device__ __forceinline__ bool verify_slice(const CrcConsts* crc, const u32 (*t8)[256], const uint8_t* base,
+                                             u64 nb16, u64 start, u64 count) {
+  const u32 lane = lane_id();
+  u64 q = 0, done = 0;  // piece of the next record start; records checked (both wave-uniform)
+  u64 wk = 0;
+  u32 W0 = slice_lens(base, nb16, 0, lane), W1 = slice_lens(base, nb16, 1, lane);
+  bool bad = false;
+  while (q < nb16 && !bad) {
+    // the next (at most 64) record starts: lane j keeps the start of record done + j
+    u64 myq = 0;
+    u32 nrec = 0;
+    while (nrec < 64u && q < nb16) {
+      const u64 k = q >> 6;
+      if (k != wk) {
+        W0 = k == wk + 1ull ? W1 : slice_lens(base, nb16, k, lane);
+        W1 = slice_lens(base, nb16, k + 1ull, lane);
+        wk = k;
+      }
+      const u32 Lq = (u32)__shfl((int)W0, (int)(q & 63ull), 64);
+      if (lane == nrec) myq = q;
+      q += 1ull + (Lq >> 4) + ((Lq & 15u) ? 1u : 0u);
+      ++nrec;
+    }
+    q = bcast_u64(q, 0);  // (uniform by construction)
+    const bool in = lane < nrec;
+    uint4 hdr = make_uint4(0, 0, 0, 0);
+    u32 L = 0, m = 0;
+    bool chk = false;
+    if (in) {
+      hdr = *reinterpret_cast<const uint4*>(base + 16ull * myq);
+      L = hdr.z;
+      m = (L >> 4) + ((L & 15u) ? 1u : 0u);
+      const u64 off = ((u64)hdr.y << 32) | hdr.x;
+      chk = off == start + done + lane && done + lane < count && (u64)m <= nb16 - myq - 1ull;
+    }
+    bool fail = in && !chk;
+    const bool big = chk && m > kBigVerify;
+    const u32 mm = chk && !big ? m : 0u;
+    const uint8_t* pay = base + 16ull * (myq + 1ull);
+    u32 acc = 0xFFFFFFFFu;
+    bool padz = true;
+    for (u32 c = 0; __any(c < mm); c += 4) {
+      uint4 v[4];
+#pragma unroll
+      for (u32 u = 0; u < 4; ++u)  // four pieces in flight per lane
+        v[u] = c + u < mm ? *reinterpret_cast<const uint4*>(pay + 16ull * (c + u)) : make_uint4(0, 0, 0, 0);
+#pragma unroll
+      for (u32 u = 0; u < 4; ++u)
+        if (c + u < mm) {
+          acc = crc_step8(t8, crc_step8(t8, acc, v[u].x, v[u].y), v[u].z, v[u].w);
+          if (c + u + 1u == mm) padz = pad_zero16(v[u], L);
+        }
+    }
+    for (u64 bm = __ballot(big); bm; bm &= bm - 1ull) {
+      const u32 sl = (u32)__builtin_ctzll(bm);
+      const uint8_t* bpay = reinterpret_cast<const uint8_t*>(bcast_u64(reinterpret_cast<u64>(pay), sl));
+      const u32 bm16 = (u32)__builtin_amdgcn_readlane((int)m, (int)sl);  // (at most the slice's pieces)
+      const u32 bacc = wave_crc_pieces(crc, t8, bm16,
+                                       [&](u32 jp) { return *reinterpret_cast<const uint4*>(bpay + 16ull * jp); });
+      if (lane == sl) acc = bacc;
+    }
+    if (chk) {
+      if (big) padz = pad_zero16(*reinterpret_cast<const uint4*>(pay + 16ull * (m - 1u)), L);
+      fail = crc_of_padded(crc, acc, L, m) != hdr.w || !padz;
+    }
+    bad = __any(fail);
+    done += nrec;
+  }
+  return !bad && q == nb16 && done == count;
+}
+
+// A wave per request of the ticket (a grid of at most a few workgroups per CU, the waves striding
+// over the requests): a flagged request served RMQ_OK with records is checked in the output and,
+// if a record fails, its row rewritten RMQ_ECORRUPT with count 0 (start_offset, out_pos and bytes
+// stay); then the commit the gather left to this kernel, with the gather's exact rule.
+__global__ __launch_bounds__(kVT, 4) void fetch_verify_kernel(FetchVerifyArgs a) {
+  __shared__ __attribute__((aligned(16))) u32 tabs[16 * 256];  // table[8] then zshift[2][4]
+  __shared__ __attribute__((aligned(16))) u32 nibs[512];
+  crc_tables_lds<kVT>(a.crc, tabs, nibs);
+  __syncthreads();
+  const u32(*t8)[256] = reinterpret_cast<const u32(*)[256]>(tabs);
+  const u32 lane = lane_id();
+  const u32 stride = gridDim.x * (kVT / 64);
+  for (u32 r = (u32)__builtin_amdgcn_readfirstlane(blockIdx.x * (kVT / 64) + (threadIdx.x >> 6)); r < a.n; r += stride) {
+    const u32 flags = a.req_dev[4ull * r + 3];
+    if (!(flags & (kFetchVerify | 1u))) continue;  // neither checked nor committed
+    const ulonglong2 lo = *reinterpret_cast<const ulonglong2*>(a.rows + 4ull * r);
+    const ulonglong2 hi = *reinterpret_cast<const ulonglong2*>(a.rows + 4ull * r + 2);
+    const u64 w0 = bcast_u64(lo.x, 0), w1 = bcast_u64(lo.y, 0), w2 = bcast_u64(hi.x, 0);
+    const int status = (int)(u32)bcast_u64(hi.y, 0);
+    const u64 count = (u32)w2, bytes = w2 >> 32;
+    bool refused = false;
+    if ((flags & kFetchVerify) && status == kOk && count) {
+      refused = !verify_slice(a.crc, t8, a.out + w1, bytes >> 4, w0, count);
+      if (refused && lane == 0)
+        *reinterpret_cast<ulonglong2*>(a.rows + 4ull * r + 2) = make_ulonglong2(bytes << 32, (u64)(uint32_t)kCorrupt);
+    }
+    // RMQ_FETCH_COMMIT, as the gather does it (a request that did not fit has status RMQ_ENOSPC here)
+    if (a.commits && (flags & 1u) && !refused && (status == kOk || status == kOffset) && lane == 0) {
+      const u32 p = a.req_dev[4ull * r], c = a.req_dev[4ull * r + 1];
+      const u64 nx = w0 + (status == kOk ? count : 0ull);
+      if (a.replica && (flags & kFetchReplica)) {
+        a.st.rcur[p] = nx;
+      } else {
+        a.st.cons[(u64)p * a.st.C + c] = nx;
+        a.st.cdirty[p] = 1u;
+      }
+    }
+  }
+}
+
+void launch_fetch_verify(const FetchVerifyArgs& a, uint32_t max_wgs, hipStream_t s) {
+  if (!a.n) return;
+  const uint32_t wgs = std::min<uint32_t>((a.n + kVT / 64 - 1) / (kVT / 64), std::max<uint32_t>(max_wgs, 1u));
+  hipLaunchKernelGGL(fetch_verify_kernel, dim3(wgs), dim3(kVT), 0, s, a);
 }
 
 // ev[4]: start / end events of the two kernels, recorded by the dispatches themselves

@@ -335,6 +335,22 @@ struct FetchBatch {
   uint32_t nt;
 };
 constexpr uint32_t kFetchReplica = 2u;  // rmq_fetch_req.flags RMQ_FETCH_REPLICA
+constexpr uint32_t kFetchVerify = 0x20u;  // rmq_fetch_req.flags RMQ_FETCH_VERIFY
+// The third kernel of a ticket with an RMQ_FETCH_VERIFY request (its own arguments: FetchArgs and
+// the kernargs of the resolve and the gather stay as they are): it checks the flagged slices in the
+// output, rewrites the rows of the ones it refuses, and makes the ticket's commits (the gather of
+// such a ticket runs with commits = 0).
+struct FetchVerifyArgs {
+  DevState st;
+  const uint32_t* req_dev;   // [n][4] the resolve's device copy of the request rows
+  uint64_t* rows;            // [n][4] the final result rows where the gather wrote them (FetchArgs::res_host)
+  const uint8_t* out;        // the device output (the caller's, or the slot's staging of a host output)
+  const CrcConsts* crc;
+  uint32_t n;
+  uint32_t commits;          // the host checked read-and-commit requests in the call
+  uint32_t replica;          // ... and RMQ_FETCH_REPLICA requests
+  uint32_t pad;
+};
 constexpr uint32_t kCsumStride = 16;   // u64 words per chunk sum (128 bytes)
 
 
@@ -436,6 +452,19 @@ struct MigrateItem {
   uint64_t soff;                // offset of the record at spos
 };
 
+// rmq_scrub (scrub.hip, FORMAT.md §10): partitions [first, first + n).
+struct ScrubArgs {
+  DevState st;
+  const CrcConsts* crc;
+  uint64_t* tbase;   // [n + 1] exclusive scan of the partitions' task counts (plan -> verify)
+  uint64_t* rows;    // [n][4] {lowest failure key or kScrubClean, records ok, bytes ok, local replica slots}
+  uint32_t first, n;
+};
+// A failure key orders by (expected offset, replica slot, kind): offset << 5 | slot << 2 | kind
+// (offsets stay below 2^59, as the ack word's status << 62 already assumes).
+constexpr uint64_t kScrubClean = ~0ull;
+constexpr uint32_t kScrubBadCrc = 1u, kScrubBadChain = 2u;  // RMQ_SCRUB_BAD_*
+
 // launchers (defined in the .hip files)
 // start: an event the dispatch records as the kernel starts (profiling), or null
 void launch_pipeline(const PipeArgs& a, hipStream_t s, hipEvent_t start = nullptr);
@@ -446,6 +475,7 @@ void launch_late_retention(const LateArgs& a, hipStream_t s);
 void launch_become_leader(const DevState& st, uint32_t pidx, hipStream_t s);
 void launch_fetch(const FetchArgs& a, hipStream_t s, const hipEvent_t* ev4);
 void launch_fetch_batch(const FetchArgs* t, uint32_t nt, hipStream_t s);  // nt <= kFetchBatch tickets, one pair
+void launch_fetch_verify(const FetchVerifyArgs& a, uint32_t max_wgs, hipStream_t s);  // after the ticket's gather
 void preload_fetch_kernels();
 
 void launch_consumer_commit(const ConsumerCommitArgs& a, hipStream_t s);
@@ -461,6 +491,7 @@ void launch_ack_apply(const AckApplyArgs& a, hipStream_t s);
 void launch_notice_fill(const NoticeArgs& a, hipStream_t s);   // leader: {commit, term} per out entry
 void launch_notice_apply(const NoticeArgs& a, hipStream_t s);  // follower: learn the leader's commit
 void launch_flip(uint8_t* region, uint64_t size, int64_t at, hipStream_t s);  // rmq_fault_corrupt
+void launch_scrub(const ScrubArgs& a, uint32_t verify_wgs, hipStream_t s);  // plan, then verify on verify_wgs workgroups
 
 }  // namespace rmq
 

@@ -58,6 +58,10 @@ FETCH_RES_DTYPE = np.dtype([
     ("start_offset", "<u8"), ("out_pos", "<u8"), ("count", "<u4"), ("bytes", "<u4"),
     ("status", "<i4"), ("reserved", "<u4"),
 ])
+SCRUB_RES_DTYPE = np.dtype([
+    ("records_ok", "<u8"), ("bytes_ok", "<u8"), ("bad_offset", "<u8"), ("bad_replica", "<u4"),
+    ("bad_kind", "<u4"), ("replicas", "<u4"), ("status", "<i4"),
+])
 STATE_FIELDS = ("log_end_offset", "log_end_pos", "log_start_offset", "log_start_pos", "commit",
                 "high_watermark", "term", "term_start", "leader_commit", "last_log_term", "voted_term",
                 "voted_for", "led", "heard_round")
@@ -131,6 +135,7 @@ class Engine:
         self._dargs = (C.byref(self._dbatch), C.byref(self._dticket))
         self.transport = False  # a replication transport is attached (rounds are collective)
         self.last_offset_ticket = 0
+        self.last_scrub_rc = A.RMQ_OK
 
     def close(self) -> None:
         if getattr(self, "h", None):
@@ -374,15 +379,17 @@ class Engine:
         return rc
 
     def fetch(self, pidx, consumer, max_records, out_cap: int | None = None, commit: bool = False,
-              out: np.ndarray | None = None, replica: bool = False):
+              out: np.ndarray | None = None, replica: bool = False, verify: bool = False):
         """rmq_fetch into a host array (sized by a first call when out_cap is None, or the caller's
         uint8 `out`, e.g. page-locked from host_empty: one call, RMQ_ENOSPC if it is too small);
         commit: RMQ_FETCH_COMMIT on every request (the size query commits nothing); replica:
-        RMQ_FETCH_REPLICA (this engine's own replica from its replica cursor, leader or follower)."""
+        RMQ_FETCH_REPLICA (this engine's own replica from its replica cursor, leader or follower);
+        verify: RMQ_FETCH_VERIFY (a slice with a record that fails its checks comes back
+        RMQ_ECORRUPT with count 0)."""
         n = len(pidx)
         req = np.zeros((n, 4), np.uint32)
         req[:, 0], req[:, 1], req[:, 2] = pidx, consumer, max_records
-        req[:, 3] = A.RMQ_FETCH_REPLICA if replica else 0
+        req[:, 3] = (A.RMQ_FETCH_REPLICA if replica else 0) | (A.RMQ_FETCH_VERIFY if verify else 0)
         res = np.zeros(n, FETCH_RES_DTYPE)
         if out is not None:
             if commit:
@@ -410,12 +417,13 @@ class Engine:
 
     def fetch_device(self, pidx, consumer, max_records, d_out: int, out_cap: int, commit: bool = False,
                      req: np.ndarray | None = None, res: np.ndarray | None = None, pinned_rows: bool = False,
-                     d_rows: tuple[int, int, int] | None = None):
+                     d_rows: tuple[int, int, int] | None = None, verify: bool = False):
         """rmq_fetch into a device buffer (16-byte aligned); returns (rc, res, bytes_used). req / res:
         the caller's arrays (pidx / consumer / max_records None leave req's columns as they are);
         pinned_rows: page-locked ones (fetch_rows), read and written by the kernels in place
         (RMQ_FETCH_PINNED_ROWS). d_rows = (n, device request rows, device result rows): rows in
-        device memory (RMQ_FETCH_DEVICE_ROWS, flags ignored); res is then None."""
+        device memory (RMQ_FETCH_DEVICE_ROWS, flags ignored); res is then None. verify:
+        RMQ_FETCH_VERIFY on every request (host rows only)."""
         if d_rows is not None:
             n, d_req, d_res = d_rows
             used = C.c_uint64()
@@ -428,6 +436,8 @@ class Engine:
         if req is None:
             req = np.zeros((n, 4), np.uint32)
             req[:, 3] = A.RMQ_FETCH_COMMIT if commit else 0
+        if verify:
+            req[:, 3] |= A.RMQ_FETCH_VERIFY
         for col, v in ((0, pidx), (1, consumer), (2, max_records)):
             if v is not None:
                 req[:, col] = v
@@ -442,7 +452,8 @@ class Engine:
 
     def fetch_async(self, pidx, consumer, max_records, d_out: int | None = None, out_cap: int = 0,
                     out: np.ndarray | None = None, req: np.ndarray | None = None,
-                    res: np.ndarray | None = None, pinned_rows: bool = False) -> "FetchTicket":
+                    res: np.ndarray | None = None, pinned_rows: bool = False,
+                    verify: bool = False) -> "FetchTicket":
         """rmq_fetch_async into a device buffer (d_out, 16-byte aligned) or a host array (out): the
         call returns at once; fetch_poll(ticket) gives (rc, res, bytes_used) once it completes. The
         handle keeps the request, result and output arrays alive until then. req ([n, 4] uint32)
@@ -450,13 +461,15 @@ class Engine:
         given, pidx / consumer / max_records None leave those columns as they are (column 3: the
         requests' flags, RMQ_FETCH_COMMIT). pinned_rows: req and res are page-locked (fetch_rows)
         and the kernels read and write them in place (RMQ_FETCH_PINNED_ROWS); req then stays
-        unchanged until the ticket completes."""
+        unchanged until the ticket completes. verify: RMQ_FETCH_VERIFY ORed into every request."""
         n = len(pidx) if pidx is not None else len(req)
         if pinned_rows and (req is None or res is None):
             raise ValueError("pinned_rows needs the caller's page-locked req and res (fetch_rows)")
         if req is None:
             req = np.empty((n, 4), np.uint32)
             req[:, 3] = 0
+        if verify:
+            req[:, 3] |= A.RMQ_FETCH_VERIFY
         for col, v in ((0, pidx), (1, consumer), (2, max_records)):
             if v is not None:
                 req[:, col] = v
@@ -533,6 +546,24 @@ class Engine:
         out = np.empty((n, self.cfg.max_consumers), np.uint64)
         _check(self.lib.rmq_read_consumer_table(self.h, first, n, _ptr(out)), "rmq_read_consumer_table")
         return out
+
+    def scrub(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """rmq_scrub: the on-device audit of the retained logs of partitions [first, first + n), every
+        local replica slot (FORMAT.md §10): a structured array of rmq_scrub_res, one row per
+        partition. Corruption raises nothing (the rows say where it is); self.last_scrub_rc keeps
+        the call's return value, RMQ_OK or RMQ_ECORRUPT. Drains first (collective with a transport)."""
+        n = self.cfg.num_partitions - first if n is None else n
+        out = np.zeros(max(n, 0), SCRUB_RES_DTYPE)
+        rc = self.lib.rmq_scrub(self.h, first, n, _ptr(out) if n else None)
+        if rc not in (A.RMQ_OK, A.RMQ_ECORRUPT):
+            raise EngineError(rc, "rmq_scrub")
+        self.last_scrub_rc = rc
+        return out
+
+    def fault_flip_ring(self, replica: int, pidx: int, ring_off: int, xor_mask: int = 0x5A) -> None:
+        """Tests: XOR one byte of a local replica ring (rmq_fault_flip_ring), addressed as
+        read_segment addresses it."""
+        _check(self.lib.rmq_fault_flip_ring(self.h, replica, pidx, ring_off, xor_mask), "rmq_fault_flip_ring")
 
     def consumer_offsets(self, pidx: int) -> np.ndarray:
         out = np.empty(self.cfg.max_consumers, np.uint64)

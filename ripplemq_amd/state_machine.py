@@ -117,12 +117,21 @@ class MessageBatchReadRequest:
 class MessageBatchReadResponse:
     messages: list = field(default_factory=list)
     offset: int = 0
+    # (not in the reference's response: a read the engine refused, e.g. RMQ_ECORRUPT under `verify`)
+    success: bool = True
+    errorMsg: str | None = None
 
     def getMessages(self):
         return self.messages
 
     def getOffset(self) -> int:
         return self.offset
+
+    def isSuccess(self) -> bool:
+        return self.success
+
+    def getErrorMsg(self):
+        return self.errorMsg
 
 
 def _encode(m) -> bytes:
@@ -172,8 +181,11 @@ class PartitionBroker:
 
     def __init__(self, directory: PartitionDirectory, engine=None, *, replication_factor: int = 1,
                  segment_bytes: int = 1 << 22, index_interval: int = 4096, device: int = 0,
-                 messages_as_str: bool = True, durable=None):
-        """durable: a ``ripplemq_amd.tier.DurableLog`` over this engine, or None. With it, a read
+                 messages_as_str: bool = True, durable=None, verify: bool = False):
+        """verify: reads carry RMQ_FETCH_VERIFY, and a slice with a record that fails its CRC32C or
+        framing is answered by a failed MessageBatchReadResponse (no messages, the offset the
+        consumer stands at, an error message) instead of being served. Off by default.
+        durable: a ``ripplemq_amd.tier.DurableLog`` over this engine, or None. With it, a read
         below a ring's retained start is served from the segment files (the reference never
         evicts, PartitionStateMachine.java:26) instead of failing with RMQ_EOFFSET."""
         self.dir = directory
@@ -185,6 +197,7 @@ class PartitionBroker:
             engine = Engine(cfg)
         self.engine = engine
         self.as_str = messages_as_str
+        self.verify = bool(verify)
         self._sms: dict[str, PartitionStateMachine] = {}
 
     def close(self) -> None:
@@ -302,7 +315,7 @@ class PartitionBroker:
             mx.append(max(int(req.getMaxMessages()), 0))
         if idx:
             _, res, buf, _ = self.engine.fetch(np.asarray(p, np.uint32), np.asarray(c, np.uint32),
-                                               np.asarray(mx, np.uint32))
+                                               np.asarray(mx, np.uint32), **({"verify": True} if self.verify else {}))
             spilled = False
             for k, r in enumerate(idx):
                 st = int(res["status"][k])
@@ -321,6 +334,10 @@ class PartitionBroker:
                     hw = int(self.engine.state(p[k])["high_watermark"])
                     recs = self.durable.read(p[k], off, min(mx[k], hw - off))
                     out[r] = MessageBatchReadResponse([_decode(b, self.as_str) for _, _, b in recs], off)
+                    continue
+                if st == A.RMQ_ECORRUPT:  # (only under verify: the slice failed its checks, nothing is served)
+                    out[r] = MessageBatchReadResponse([], int(res["start_offset"][k]), False,
+                                                      f"Corrupt record in {requests[r].getGroupId()}")
                     continue
                 if st != A.RMQ_OK:
                     raise EngineError(st, f"fetch {requests[r].getGroupId()}")
