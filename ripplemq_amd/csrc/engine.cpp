@@ -787,6 +787,7 @@ int rmq_create(const rmq_config* cfg, rmq_engine** out) {
   e->verify_wgs = verify_wgs_per_cu() * e->cu_count;
   if (const char* v = std::getenv("RMQ_VERIFY_WGS")) e->verify_wgs = std::max(1, std::atoi(v));
   if (const char* v = std::getenv("RMQ_BIG_WGS")) e->big_wgs = (uint32_t)std::atoi(v);
+  if (const char* v = std::getenv("RMQ_AUDIT_WGS")) e->audit_wgs = (uint32_t)std::max(0, std::atoi(v));
   std::snprintf(e->dev_name, sizeof e->dev_name, "%s (%s)", prop.name, prop.gcnArchName);
   if (e->split && e->rank_cus && e->rank_cus < e->cu_count) {
     // CU masks (bit i = the i-th CU in the runtime's numbering): the rank stream takes the first
@@ -1724,6 +1725,13 @@ int fetch_slot_step(rmq_engine* e, rmq_engine::FetchSlot& f, bool wait, uint64_t
 }  // namespace
 
 namespace {
+// Workgroups of the two audit kernels (the scrub's verify, the fetch verify): 8 per CU, or at most
+// RMQ_AUDIT_WGS of them.
+uint32_t audit_wgs(const rmq_engine* e) {
+  const uint32_t wgs = std::max<uint32_t>(e->cu_count, 1u) * 8u;
+  return e->audit_wgs ? std::min(wgs, e->audit_wgs) : wgs;
+}
+
 // Issue a fetch into the next slot: its kernels on the pipeline stream, an event after them.
 int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t mem, uint8_t* out,
                 uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket, bool sync) {
@@ -1917,7 +1925,7 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t m
       v.n = n;
       v.commits = any ? 1u : 0u;
       v.replica = a.replica;
-      launch_fetch_verify(v, std::max<uint32_t>(e->cu_count, 1u) * 8u, e->main_s);
+      launch_fetch_verify(v, audit_wgs(e), e->main_s);
       HIP_TRY(hipGetLastError());
     }
     if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
@@ -2173,7 +2181,7 @@ int rmq_scrub(rmq_engine* e, uint32_t first, uint32_t n, rmq_scrub_res* res) {
   }
   // the tasks are counted on the device (the plan), so the verify grid is a fixed few workgroups
   // per CU whose waves stride over them
-  launch_scrub(a, std::max<uint32_t>(e->cu_count, 1u) * 8u, e->main_s);
+  launch_scrub(a, audit_wgs(e), e->main_s);
   HIP_TRY(hipGetLastError());
   if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
   rc = stream_wait(e->main_s);

@@ -596,6 +596,15 @@ __global__ __launch_bounds__(kVT, 4) void fetch_verify_kernel(FetchVerifyArgs a)
       if (refused && lane == 0)
         *reinterpret_cast<ulonglong2*>(a.rows + 4ull * r + 2) = make_ulonglong2(bytes << 32, (u64)(uint32_t)kCorrupt);
     }
+    // A flagged request that is not served, refused here or too large for the output (its size
+    // comes from the same walk), leaves no position cache entry: the resolve stored one from length
+    // words nothing has checked, so the consumer's next fetch takes the index search (FORMAT.md
+    // §10; the resolve found records for both, so their partition and consumer are in range)
+    if ((flags & kFetchVerify) && (refused || status == kNoSpc) && lane == 0) {
+      const u32 p = a.req_dev[4ull * r], c = a.req_dev[4ull * r + 1];
+      if (p < a.st.P && c < a.st.C)
+        *reinterpret_cast<ulonglong2*>(a.st.pcache + ((u64)p * a.st.C + c) * 2) = make_ulonglong2(~0ull, 0ull);
+    }
     // RMQ_FETCH_COMMIT, as the gather does it (a request that did not fit has status RMQ_ENOSPC here)
     if (a.commits && (flags & 1u) && !refused && (status == kOk || status == kOffset) && lane == 0) {
       const u32 p = a.req_dev[4ull * r], c = a.req_dev[4ull * r + 1];
