@@ -50,6 +50,33 @@ def compare_state(dev, ora, cfg, parts=None, full_rings=False, local_slots=None)
         assert np.array_equal(dev.consumer_offsets(p), ora.consumer_offsets(p)), f"consumer offsets p={p}"
 
 
+def index_capacity(cfg, seg):
+    """Entries of the index ring of a log ring of `seg` bytes (FORMAT.md §5: icap)."""
+    return (2 * (cfg.pipeline_depth or 2) + 2) * seg // cfg.index_interval
+
+
+def expected_index_slots(ora, cfg, p):
+    """Every slot of p's index ring as a ring move leaves it (FORMAT.md §2): slot m mod icap holds the
+    oracle's E[m] for the live m, every other slot {0, 0}."""
+    st = ora.state(p)
+    I, icap = cfg.index_interval, index_capacity(cfg, st["segment_bytes"])
+    want = np.zeros((icap, 2), np.uint64)
+    m_lo, m_hi = -(-st["log_start_pos"] // I), st["log_end_pos"] // I
+    assert m_hi - m_lo + 1 <= icap
+    if m_hi >= m_lo:
+        want[np.arange(m_lo, m_hi + 1) % icap] = ora.read_index(p, m_lo, m_hi - m_lo + 1)
+    return want
+
+
+def compare_index_slots(dev, ora, cfg, p):
+    want = expected_index_slots(ora, cfg, p)
+    got = dev.read_index(p, 0, len(want))
+    if not np.array_equal(got, want):
+        bad = np.flatnonzero((got != want).any(axis=1))
+        raise AssertionError(f"index slots p={p}: {bad.size} of {len(want)} differ, first {bad[:4]}: "
+                             f"gpu={got[bad[:4]].tolist()} want={want[bad[:4]].tolist()}")
+
+
 def run_ops(dev, ora, cfg, ops, check=True, full_rings=False, parts=None, local_slots=None):
     """Apply ops to both engines, comparing outputs of every op and state after each append."""
     log = []
@@ -77,8 +104,9 @@ def run_ops(dev, ora, cfg, ops, check=True, full_rings=False, parts=None, local_
             assert rd == ro and np.array_equal(std, sto), (rd, ro, std, sto)
         elif kind == "fetch":
             out_cap = op[4] if len(op) > 4 else None
-            rd, resd, bd, ud = dev.fetch(op[1], op[2], op[3], out_cap)
-            ro, reso, bo, uo = ora.fetch(op[1], op[2], op[3], out_cap)
+            commit = bool(op[5]) if len(op) > 5 else False  # RMQ_FETCH_COMMIT on every request
+            rd, resd, bd, ud = dev.fetch(op[1], op[2], op[3], out_cap, commit=commit)
+            ro, reso, bo, uo = ora.fetch(op[1], op[2], op[3], out_cap, commit=commit)
             assert rd == ro, (rd, ro)
             assert ud == uo, (ud, uo)
             if not np.array_equal(resd, reso):
