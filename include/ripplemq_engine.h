@@ -460,6 +460,34 @@ int rmq_scrub(rmq_engine* e, uint32_t first, uint32_t n, rmq_scrub_res* res);
    or a zero mask. Drains first (collective with a transport, like rmq_sync). */
 int rmq_fault_flip_ring(rmq_engine* e, uint32_t replica, uint32_t pidx, uint64_t ring_off, uint32_t xor_mask);
 
+/* ---- repair (added after ABI 11 without a bump: one struct, one flag and one function, and no
+   existing struct, value or behaviour moves, so every ABI 11 caller still links and runs) ---- */
+#define RMQ_REPAIR_DRY_RUN 1u   /* find and count, write nothing */
+typedef struct rmq_repair_res {
+  uint64_t segments_repaired;    /* (local slot, segment) pairs rewritten from a clean local slot */
+  uint64_t bytes_repaired;       /* their segment bytes (end - pos of each) */
+  uint64_t segments_unrepaired;  /* failing pairs with no passing local slot for that segment: left as they were */
+  uint64_t bad_offset;           /* what remains AFTER the call, as rmq_scrub_res reports it */
+  uint32_t bad_replica;
+  uint32_t bad_kind;
+  uint32_t replicas;
+  int32_t status;                /* RMQ_OK, or RMQ_ECORRUPT if something remains */
+} rmq_repair_res;                /* 48 bytes */
+/* Scrub, then repair, then scrub again (FORMAT.md §10 "Repair"): audits partitions [first, first + n)
+   as the scrub does, and overwrites the bytes of every (local slot, segment) pair that fails with
+   those of the lowest local slot on which the same segment passes. Nothing else is written: bytes
+   outside retained segments, passing pairs, index entries, partition state, consumer offsets and
+   the position cache stay. A failing pair with no passing local slot (a single local slot, damage
+   on every slot, a damaged index entry or partition state) is counted in segments_unrepaired and
+   left alone. The range is then audited again: bad_offset, bad_replica, bad_kind, replicas and
+   status are the scrub's row of the state the call leaves. With RMQ_REPAIR_DRY_RUN the counters
+   are those the real call would return, the other fields describe the present state and no ring
+   byte changes. res (host, [n], nullable). Returns RMQ_OK if every partition of the range is clean
+   afterwards, RMQ_ECORRUPT if any is not, RMQ_ENOPART if the range leaves [0, P), RMQ_EINVAL for an
+   unknown flag bit. Drains first: with a transport attached the call is collective, and each rank
+   repairs only the slots it holds. */
+int rmq_repair(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags, rmq_repair_res* res);
+
 /* ---- host utilities ---- */
 /* FORMAT.md §1 records laid back to back in host memory (segment files of a durable tier, fetch
    output): walks them from buf[0], expecting header offsets first, first + 1, ..., and stops at the
@@ -502,7 +530,8 @@ int rmq_host_unregister(rmq_engine* e, void* p);
    copy or host gap inflates and a rocprofv3 trace shows the kernels back to back; a fetch with an
    RMQ_FETCH_COMMIT or RMQ_FETCH_VERIFY request runs once (each run would commit; the verify
    rewrites the rows). 2: rmq_scrub, an event before its first kernel (the plan) to one after its last
-   (the verify), launches = calls. */
+   (the verify), launches = calls. 5: rmq_repair, likewise from before its first kernel to after its
+   last, launches = calls. */
 int rmq_profile_enable(rmq_engine* e, int enable);
 int rmq_profile_query(rmq_engine* e, int kernel, uint64_t* launches, double* total_ms);
 /* Device name / CU count for reports. */

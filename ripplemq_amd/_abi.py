@@ -29,6 +29,7 @@ RMQ_TICKET_OFFSETS = 1 << 63
 RMQ_SCAN_CHECK = 1
 RMQ_SCRUB_BAD_CRC = 1
 RMQ_SCRUB_BAD_CHAIN = 2
+RMQ_REPAIR_DRY_RUN = 1
 
 RMQ_OK = 0
 RMQ_PENDING = 1
@@ -114,6 +115,13 @@ class RmqScrubRes(C.Structure):
     ]
 
 
+class RmqRepairRes(C.Structure):
+    _fields_ = [
+        ("segments_repaired", u64), ("bytes_repaired", u64), ("segments_unrepaired", u64),
+        ("bad_offset", u64), ("bad_replica", u32), ("bad_kind", u32), ("replicas", u32), ("status", i32),
+    ]
+
+
 class RmqAppendStats(C.Structure):
     _fields_ = [
         ("records", u32), ("appended", u32), ("rejected_not_leader", u32),
@@ -179,6 +187,7 @@ _SIGS = {
     "rmq_fault_cut": (C.c_int, [vp, u32, u32]),
     "rmq_scrub": (C.c_int, [vp, u32, u32, vp]),
     "rmq_fault_flip_ring": (C.c_int, [vp, u32, u32, u64, u32]),
+    "rmq_repair": (C.c_int, [vp, u32, u32, u32, vp]),
     "rmq_scan_records": (C.c_int, [vp, u64, u64, u64, u32, vp, C.POINTER(u64), C.POINTER(u64)]),
     "rmq_tier_append": (C.c_int, [u32, vp, vp, vp, vp, vp, vp, vp, u32, C.c_int]),
 }

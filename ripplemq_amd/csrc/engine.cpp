@@ -594,7 +594,8 @@ void free_engine(rmq_engine* e) {
   std::vector<void*> bufs = {s.start_off, s.start_pos, s.commit, s.hw, s.term_start, s.term, s.match, s.is_leader,
                              s.local_mask, s.index, s.logs, s.ring, s.cons, s.pcache, s.rcur, s.cdirty, s.lcommit, s.csnap, s.cver, s.cq,
                              s.lterm, s.mterm, s.heard, e->d_crc,
-                             e->d_stats, e->d_ctl32, e->d_ctl64, e->d_stamps, e->d_rlate, e->d_scrub_tbase, e->d_scrub_rows};
+                             e->d_stats, e->d_ctl32, e->d_ctl64, e->d_stamps, e->d_rlate, e->d_scrub_tbase, e->d_scrub_rows,
+                             e->d_repair_verdict, e->d_repair_counts};
   if (e->state_stage) hipHostFree(e->state_stage);
   for (rmq_engine::FetchSlot& f : e->fslot) {
     void* fs[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_out};
@@ -2146,6 +2147,20 @@ int rmq_read_consumer_table(rmq_engine* e, uint32_t first, uint32_t n, uint64_t*
   return RMQ_OK;
 }
 
+// The plan's scan and the result rows of a range of n partitions (rmq_scrub, rmq_repair).
+static int scrub_buffers(rmq_engine* e, uint32_t n) {
+  if (e->scrub_cap >= n) return RMQ_OK;
+  if (e->d_scrub_tbase) hipFree(e->d_scrub_tbase);
+  if (e->d_scrub_rows) hipFree(e->d_scrub_rows);
+  e->d_scrub_tbase = e->d_scrub_rows = nullptr;
+  e->scrub_cap = 0;
+  int rc = dalloc(&e->d_scrub_tbase, (size_t)n + 1);
+  if (!rc) rc = dalloc(&e->d_scrub_rows, (size_t)n * 4);
+  if (rc) return rc;
+  e->scrub_cap = n;
+  return RMQ_OK;
+}
+
 int rmq_scrub(rmq_engine* e, uint32_t first, uint32_t n, rmq_scrub_res* res) {
   if (!e) return RMQ_EINVAL;
   EngineLock g(e);
@@ -2155,16 +2170,8 @@ int rmq_scrub(rmq_engine* e, uint32_t first, uint32_t n, rmq_scrub_res* res) {
   HIP_TRY(hipSetDevice(e->device));
   int rc = drain(e);  // (fetches run on the pipeline stream: the drain waited for them too)
   if (rc) return rc;
-  if (e->scrub_cap < n) {
-    if (e->d_scrub_tbase) hipFree(e->d_scrub_tbase);
-    if (e->d_scrub_rows) hipFree(e->d_scrub_rows);
-    e->d_scrub_tbase = e->d_scrub_rows = nullptr;
-    e->scrub_cap = 0;
-    rc = dalloc(&e->d_scrub_tbase, (size_t)n + 1);
-    if (!rc) rc = dalloc(&e->d_scrub_rows, (size_t)n * 4);
-    if (rc) return rc;
-    e->scrub_cap = n;
-  }
+  rc = scrub_buffers(e, n);
+  if (rc) return rc;
   ScrubArgs a{};
   a.st = e->st;
   a.crc = e->d_crc;
@@ -2197,6 +2204,96 @@ int rmq_scrub(rmq_engine* e, uint32_t first, uint32_t n, rmq_scrub_res* res) {
     std::memset(&x, 0, sizeof x);
     x.records_ok = rows[4ull * i + 1];
     x.bytes_ok = rows[4ull * i + 2];
+    x.replicas = (uint32_t)rows[4ull * i + 3];
+    x.bad_offset = key == kScrubClean ? RMQ_OFFSET_NONE : key >> 5;
+    x.bad_replica = key == kScrubClean ? 0u : (uint32_t)(key >> 2) & 7u;
+    x.bad_kind = key == kScrubClean ? 0u : (uint32_t)key & 3u;
+    x.status = key == kScrubClean ? RMQ_OK : RMQ_ECORRUPT;
+  }
+  return corrupt ? RMQ_ECORRUPT : RMQ_OK;
+}
+
+int rmq_repair(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags, rmq_repair_res* res) {
+  if (!e || (flags & ~RMQ_REPAIR_DRY_RUN)) return RMQ_EINVAL;
+  EngineLock g(e);
+  const uint32_t P = e->cfg.num_partitions, RF = e->cfg.replication_factor;
+  if (first > P || n > P - first) return RMQ_ENOPART;
+  if (!n) return RMQ_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  int rc = drain(e);
+  if (rc) return rc;
+  rc = scrub_buffers(e, n);
+  if (rc) return rc;
+  // a verdict per task: a partition has at most ring bytes / interval + 2 segments on each of its
+  // local slots, RF at the most
+  uint64_t tasks = 0;
+  for (uint32_t p = first; p < first + n; ++p)
+    tasks += RF * (((1ull << (e->ring[p] & 63ull)) >> e->st.interval_log2) + 2ull);
+  if (e->repair_verdict_cap < tasks) {
+    if (e->d_repair_verdict) hipFree(e->d_repair_verdict);
+    e->d_repair_verdict = nullptr;
+    e->repair_verdict_cap = 0;
+    rc = dalloc(&e->d_repair_verdict, (size_t)tasks);
+    if (rc) return rc;
+    e->repair_verdict_cap = tasks;
+  }
+  if (e->repair_counts_cap < n) {
+    if (e->d_repair_counts) hipFree(e->d_repair_counts);
+    e->d_repair_counts = nullptr;
+    e->repair_counts_cap = 0;
+    rc = dalloc(&e->d_repair_counts, (size_t)n * 3);
+    if (rc) return rc;
+    e->repair_counts_cap = n;
+  }
+  RepairArgs a{};
+  a.s.st = e->st;
+  a.s.crc = e->d_crc;
+  a.s.tbase = e->d_scrub_tbase;
+  a.s.rows = e->d_scrub_rows;
+  a.s.first = first;
+  a.s.n = n;
+  a.verdict = e->d_repair_verdict;
+  a.counts = e->d_repair_counts;
+  a.write = (flags & RMQ_REPAIR_DRY_RUN) ? 0u : 1u;
+  hipEvent_t r0 = nullptr, r1 = nullptr;
+  if (e->profile) {  // kernel 5: an event before the first plan to one after the last kernel of the call
+    r0 = pool_event(e);
+    r1 = pool_event(e);
+    e->prof[5].push_back({r0, r1});
+    HIP_TRY(hipEventRecord(r0, e->main_s));
+  }
+  // first pass: the scrub with a verdict per task
+  launch_repair_scan(a, audit_wgs(e), e->main_s);
+  HIP_TRY(hipGetLastError());
+  if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));  // (recorded again below if more kernels follow)
+  rc = stream_wait(e->main_s);
+  if (rc) return rc;
+  std::vector<uint64_t> rows((size_t)n * 4), counts((size_t)n * 3, 0);
+  HIP_TRY(hipMemcpy(rows.data(), e->d_scrub_rows, rows.size() * 8, hipMemcpyDeviceToHost));
+  bool corrupt = false;
+  for (uint32_t i = 0; i < n && !corrupt; ++i) corrupt = rows[4ull * i] != kScrubClean;
+  if (corrupt) {
+    // the repair kernel on the same plan, then (unless nothing may be written) the audit again
+    HIP_TRY(hipMemsetAsync(e->d_repair_counts, 0, counts.size() * 8, e->main_s));
+    launch_repair_copy(a, audit_wgs(e), e->main_s);
+    if (a.write) launch_scrub(a.s, audit_wgs(e), e->main_s);
+    HIP_TRY(hipGetLastError());
+    if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
+    rc = stream_wait(e->main_s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(counts.data(), e->d_repair_counts, counts.size() * 8, hipMemcpyDeviceToHost));
+    if (a.write) HIP_TRY(hipMemcpy(rows.data(), e->d_scrub_rows, rows.size() * 8, hipMemcpyDeviceToHost));
+  }
+  corrupt = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t key = rows[4ull * i];
+    corrupt = corrupt || key != kScrubClean;
+    if (!res) continue;
+    rmq_repair_res& x = res[i];
+    std::memset(&x, 0, sizeof x);
+    x.segments_repaired = counts[3ull * i];
+    x.bytes_repaired = counts[3ull * i + 1];
+    x.segments_unrepaired = counts[3ull * i + 2];
     x.replicas = (uint32_t)rows[4ull * i + 3];
     x.bad_offset = key == kScrubClean ? RMQ_OFFSET_NONE : key >> 5;
     x.bad_replica = key == kScrubClean ? 0u : (uint32_t)(key >> 2) & 7u;
@@ -2283,7 +2380,7 @@ int rmq_profile_enable(rmq_engine* e, int enable) {
 }
 
 int rmq_profile_query(rmq_engine* e, int kernel, uint64_t* launches, double* total_ms) {
-  if (!e || kernel < 0 || kernel > 4) return RMQ_EINVAL;
+  if (!e || kernel < 0 || kernel > 5) return RMQ_EINVAL;
   EngineLock g(e);
   HIP_TRY(hipSetDevice(e->device));
   int rc = settle(e);

@@ -403,18 +403,23 @@ struct rmq_engine {
   uint32_t ctl_cap = 0;
   // profiling: pipeline launches are timed as one region (event before the first launch after
   // enable, event at the next drain) so no per-launch events sit between kernels; fetch kernels
-  // keep per-launch event pairs (prof[3], prof[4]), and so does every rmq_scrub (prof[2])
+  // keep per-launch event pairs (prof[3], prof[4]), and so do every rmq_scrub (prof[2]) and every rmq_repair (prof[5])
   uint32_t profile = 0;
   uint32_t fetch_replay = 1;     // rmq_profile_enable(k >= 2): each fetch's kernels run k times
   uint64_t prof_fetch_runs = 0;
   uint64_t prof_launches = 0, prof_batches = 0;
   hipEvent_t prof_t0 = nullptr, prof_t1 = nullptr;
   bool prof_started = false, prof_ended = false;
-  std::vector<EvPair> prof[5];
+  std::vector<EvPair> prof[6];
   // rmq_scrub: the plan's scan and the result rows of the partitions of one call (grown on demand)
   uint64_t* d_scrub_tbase = nullptr;
   uint64_t* d_scrub_rows = nullptr;
   uint32_t scrub_cap = 0;
+  // rmq_repair: a verdict byte per task of the first pass and the counters of the range's partitions
+  uint8_t* d_repair_verdict = nullptr;
+  uint64_t repair_verdict_cap = 0;
+  uint64_t* d_repair_counts = nullptr;
+  uint32_t repair_counts_cap = 0;
   std::vector<hipEvent_t> ev_pool;
   // diagnostics: RMQ_STAMPS=<csv> records per-wave phase stamps of launch RMQ_STAMPS_AT (default 100)
   const char* stamps_path = nullptr;

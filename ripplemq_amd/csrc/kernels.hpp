@@ -465,6 +465,15 @@ struct ScrubArgs {
 constexpr uint64_t kScrubClean = ~0ull;
 constexpr uint32_t kScrubBadCrc = 1u, kScrubBadChain = 2u;  // RMQ_SCRUB_BAD_*
 
+// rmq_repair (repair.hip, FORMAT.md §10 "Repair"): the scrub's plan and rows, a verdict per task
+// and the counters of the partitions of the range.
+struct RepairArgs {
+  ScrubArgs s;
+  uint8_t* verdict;   // [tasks] kVerdictPass / kVerdictFail of the first pass
+  uint64_t* counts;   // [n][3] {segments repaired, their bytes, segments unrepaired}
+  uint32_t write;     // 0: count only (RMQ_REPAIR_DRY_RUN)
+};
+
 // launchers (defined in the .hip files)
 // start: an event the dispatch records as the kernel starts (profiling), or null
 void launch_pipeline(const PipeArgs& a, hipStream_t s, hipEvent_t start = nullptr);
@@ -492,6 +501,9 @@ void launch_notice_fill(const NoticeArgs& a, hipStream_t s);   // leader: {commi
 void launch_notice_apply(const NoticeArgs& a, hipStream_t s);  // follower: learn the leader's commit
 void launch_flip(uint8_t* region, uint64_t size, int64_t at, hipStream_t s);  // rmq_fault_corrupt
 void launch_scrub(const ScrubArgs& a, uint32_t verify_wgs, hipStream_t s);  // plan, then verify on verify_wgs workgroups
+void launch_scrub_plan(const ScrubArgs& a, hipStream_t s);
+void launch_repair_scan(const RepairArgs& a, uint32_t wgs, hipStream_t s);  // plan, then verify with verdicts
+void launch_repair_copy(const RepairArgs& a, uint32_t wgs, hipStream_t s);
 
 }  // namespace rmq
 

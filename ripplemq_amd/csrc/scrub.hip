@@ -10,51 +10,14 @@
 // whole wave, one at a time, with the 1 KB Horner shift. A hot partition's log is thousands of
 // segments, so it spreads over as many lanes as it has intervals.
 //
-// Bounds: every ring read is masked with S_p - 1 of that partition's ring (ring_ref), a record's
-// piece count is clamped by the pieces left in its segment before any payload piece is loaded, a
-// segment is accepted only inside [log_start_pos, log_end_pos) of a log no longer than its ring,
-// and a walk ends at its segment's end: every record is at least 16 bytes, so the iterations are
-// bounded by the segment's span. No header word is an address or a loop bound without these.
-#include "device_common.hpp"
-#include "kernels.hpp"
+// The segments, the task decoding, its bounds and the verify walk live in scrub_common.hpp, which
+// the repair (repair.hip) shares.
+#include "scrub_common.hpp"
 
 namespace rmq {
 namespace {
 
-constexpr u32 kST = 256;        // threads per verify workgroup
-constexpr u32 kSW = kST / 64;   // its waves
 constexpr u32 kPlanT = 1024;    // the plan's single workgroup: a thread per partition, chunk after chunk
-constexpr u32 kBigScrub = 64;   // records over this many 16-byte pieces: the whole wave (kBigIngest)
-
-// What the plan and the verify lanes both derive of partition p: its retained log, its ring, its
-// local replica slots and the segments that tile the log (FORMAT.md §10).
-struct ScrubPart {
-  u64 so, sp, eo, ep;  // log start / end {offset, position}
-  u64 lo;              // first live index entry, ceil(sp / I)
-  u64 nseg;            // segments: 1 (no live entry, or a state no log can have), else hi - lo + 2
-  RingRef rg;
-  u32 mask;            // local replica slots
-  bool sane;           // the log lies forward, 16-byte aligned, inside one ring length
-};
-__device__ __forceinline__ ScrubPart scrub_part(const DevState& st, u32 p) {
-  ScrubPart q;
-  q.so = st.start_off[p];
-  q.sp = st.start_pos[p];
-  q.eo = st.leo[p];
-  q.ep = st.used[p];
-  q.rg = ring_ref(st, p);
-  q.mask = st.local_mask[p] & ((1u << st.RF) - 1u);
-  q.sane = q.ep >= q.sp && q.ep - q.sp <= q.rg.seg && ((q.sp | q.ep) & 15ull) == 0ull && q.eo >= q.so;
-  const u32 ilog = st.interval_log2;
-  q.lo = (q.sp + (1ull << ilog) - 1ull) >> ilog;
-  const u64 hi = q.ep >> ilog;
-  q.nseg = q.sane && q.lo <= hi ? hi - q.lo + 2ull : 1ull;
-  return q;
-}
-
-__device__ __forceinline__ u64 scrub_key(u64 off, u32 replica, u32 kind) {
-  return (off << 5) | ((u64)replica << 2) | kind;
-}
 
 }  // namespace
 
@@ -99,151 +62,15 @@ __global__ __launch_bounds__(kPlanT) void scrub_plan_kernel(ScrubArgs A) {
 __global__ __launch_bounds__(kST, 4) void scrub_verify_kernel(ScrubArgs A) {
   __shared__ __attribute__((aligned(16))) u32 tabs[16 * 256];  // table[8] then zshift[2][4]
   __shared__ __attribute__((aligned(16))) u32 nibs[512];
-  crc_tables_lds<kST>(A.crc, tabs, nibs);
-  __syncthreads();
-  const u32(*t8)[256] = reinterpret_cast<const u32(*)[256]>(tabs);
-  const DevState& st = A.st;
-  const u32 lane = threadIdx.x & 63u;
-  const u64 T = A.tbase[A.n];
-  const u64 stride = 64ull * gridDim.x * kSW;
-  for (u64 t0 = 64ull * (u32)__builtin_amdgcn_readfirstlane(blockIdx.x * kSW + (threadIdx.x >> 6)); t0 < T; t0 += stride) {
-    const u64 t = t0 + lane;
-    const bool in = t < T;
-    u32 i = ~0u, r = 0;
-    // the segment: bytes [pos, end), offsets [expect, eoff)
-    u64 pos = 0, end = 0, expect = 0, eoff = 0, rmask = 0;
-    const uint8_t* ring = st.logs;
-    u32 kind = 0;      // RMQ_SCRUB_BAD_* of the lane's failing record
-    u64 bad_off = 0;   // its expected offset
-    if (in) {
-      // the partition whose task range holds t: the largest i with tbase[i] <= t
-      u32 a = 0, b = A.n;
-      while (b - a > 1u) {
-        const u32 mid = a + ((b - a) >> 1);
-        if (A.tbase[mid] <= t) a = mid; else b = mid;
-      }
-      i = a;
-      const ScrubPart q = scrub_part(st, A.first + i);
-      const u64 tl = t - A.tbase[i];
-      const u64 ri = tl / q.nseg, s = tl - ri * q.nseg;
-      u32 mk = q.mask;
-      for (u64 k = 0; k < ri && mk; ++k) mk &= mk - 1u;  // (ri < popc(mask): the plan's count)
-      r = mk ? (u32)__builtin_ctz(mk) : 0u;
-      rmask = q.rg.seg - 1ull;
-      ring = st.logs + (u64)r * st.rstride + q.rg.base;
-      if (!q.sane) {
-        kind = kScrubBadChain;
-        bad_off = q.so;
-      } else {
-        pos = q.sp, expect = q.so, end = q.ep, eoff = q.eo;
-        if (q.nseg > 1ull) {
-          if (s > 0ull) {
-            const u64* ie = st.index + (q.rg.ibase + (q.lo + s - 1ull) % q.rg.icap) * 2;
-            expect = ie[0], pos = ie[1];
-          }
-          if (s + 1ull < q.nseg) {
-            const u64* ie = st.index + (q.rg.ibase + (q.lo + s) % q.rg.icap) * 2;
-            eoff = ie[0], end = ie[1];
-          }
-        }
-        // the entries name positions and offsets inside the log, in order
-        if (!(q.sp <= pos && pos <= end && end <= q.ep && ((pos | end) & 15ull) == 0ull && q.so <= expect &&
-              expect <= eoff && eoff <= q.eo)) {
-          kind = kScrubBadChain;
-          bad_off = expect < q.so ? q.so : expect > q.eo ? q.eo : expect;
-          pos = end = 0;
-        }
-      }
-    }
-    u64 n_ok = 0, b_ok = 0;
-    bool live = in && !kind && pos < end;
-    while (__any(live)) {
-      uint4 hdr = make_uint4(0, 0, 0, 0);
-      u32 L = 0, m = 0;
-      bool chk = false;
-      if (live) {
-        hdr = load_payload16(ring + (pos & rmask));
-        const u64 off = ((u64)hdr.y << 32) | hdr.x;
-        L = hdr.z;
-        m = (L >> 4) + ((L & 15u) ? 1u : 0u);
-        const u64 avail = ((end - pos) >> 4) - 1ull;  // pieces of the segment after this header
-        if (off != expect || (u64)m > avail) {  // out of sequence, or the record runs past its segment
-          kind = kScrubBadChain;
-          bad_off = expect;
-          live = false;
-        } else {
-          chk = true;
-        }
-      }
-      const bool big = chk && m > kBigScrub;
-      const u32 mm = chk && !big ? m : 0u;
-      const u64 pay = pos + 16ull;
-      // the CRC register over the payload pieces in order (zero-padded in the log), from ~0
-      u32 acc = 0xFFFFFFFFu;
-      bool padz = true;
-      for (u32 c = 0; __any(c < mm); c += 4) {
-        uint4 v[4];
-#pragma unroll
-        for (u32 u = 0; u < 4; ++u)  // four pieces in flight per lane
-          v[u] = c + u < mm ? load_payload16(ring + ((pay + 16ull * (c + u)) & rmask)) : make_uint4(0, 0, 0, 0);
-#pragma unroll
-        for (u32 u = 0; u < 4; ++u)
-          if (c + u < mm) {
-            acc = crc_step8(t8, crc_step8(t8, acc, v[u].x, v[u].y), v[u].z, v[u].w);
-            if (c + u + 1u == mm) padz = pad_zero16(v[u], L);
-          }
-      }
-      // large records, one at a time by the wave (the 1 KB Horner shift)
-      for (u64 bm = __ballot(big); bm; bm &= bm - 1ull) {
-        const u32 sl = (u32)__builtin_ctzll(bm);
-        const uint8_t* bring = reinterpret_cast<const uint8_t*>(bcast_u64(reinterpret_cast<u64>(ring), sl));
-        const u64 bpay = bcast_u64(pay, sl), bmask = bcast_u64(rmask, sl);
-        const u32 bm16 = (u32)__builtin_amdgcn_readlane((int)m, (int)sl);  // (at most the segment's pieces)
-        const u32 bacc = wave_crc_pieces(A.crc, t8, bm16,
-                                         [&](u32 jp) { return load_payload16(bring + ((bpay + 16ull * jp) & bmask)); });
-        if (lane == sl) acc = bacc;
-      }
-      if (chk) {
-        const u32 crc = crc_of_padded(A.crc, acc, L, m);
-        // (a large record's last piece is read again: the wave folded its pieces)
-        if (big) padz = pad_zero16(load_payload16(ring + ((pos + 16ull * m) & rmask)), L);
-        if (crc == hdr.w && padz) {
-          const u64 rs = 16ull * (1ull + m);
-          ++n_ok;
-          b_ok += rs;
-          pos += rs;
-          ++expect;
-          live = pos < end;
-        } else {
-          kind = kScrubBadCrc;
-          bad_off = expect;
-          live = false;
-        }
-      }
-    }
-    // the walk landed on the segment's end (a record never passes it): as many records as the
-    // index says
-    if (in && !kind && expect != eoff) {
-      kind = kScrubBadChain;
-      bad_off = expect < eoff ? expect : eoff;
-    }
-    if (in && kind) atomicMin(reinterpret_cast<unsigned long long*>(A.rows + 4ull * i), (unsigned long long)scrub_key(bad_off, r, kind));
-    // records and bytes that passed: one add per run of a partition's lanes in the wave
-    const u32 prev = (u32)__shfl_up((int)i, 1), next = (u32)__shfl_down((int)i, 1);
-    const u32 head = lane == 0u || prev != i ? 1u : 0u;
-    const bool tail = lane == 63u || next != i;
-    u32 f1 = head, f2 = head;
-    wave_seg_incl_scan(f1, n_ok);
-    wave_seg_incl_scan(f2, b_ok);
-    if (in && tail && n_ok) {
-      atomicAdd(reinterpret_cast<unsigned long long*>(A.rows + 4ull * i + 1), (unsigned long long)n_ok);
-      atomicAdd(reinterpret_cast<unsigned long long*>(A.rows + 4ull * i + 2), (unsigned long long)b_ok);
-    }
-  }
+  scrub_verify_body<false>(A, nullptr, tabs, nibs);
+}
+
+void launch_scrub_plan(const ScrubArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(scrub_plan_kernel, dim3(1), dim3(kPlanT), 0, s, a);
 }
 
 void launch_scrub(const ScrubArgs& a, uint32_t verify_wgs, hipStream_t s) {
-  hipLaunchKernelGGL(scrub_plan_kernel, dim3(1), dim3(kPlanT), 0, s, a);
+  launch_scrub_plan(a, s);
   hipLaunchKernelGGL(scrub_verify_kernel, dim3(verify_wgs), dim3(kST), 0, s, a);
 }
 

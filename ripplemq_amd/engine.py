@@ -62,6 +62,10 @@ SCRUB_RES_DTYPE = np.dtype([
     ("records_ok", "<u8"), ("bytes_ok", "<u8"), ("bad_offset", "<u8"), ("bad_replica", "<u4"),
     ("bad_kind", "<u4"), ("replicas", "<u4"), ("status", "<i4"),
 ])
+REPAIR_RES_DTYPE = np.dtype([
+    ("segments_repaired", "<u8"), ("bytes_repaired", "<u8"), ("segments_unrepaired", "<u8"),
+    ("bad_offset", "<u8"), ("bad_replica", "<u4"), ("bad_kind", "<u4"), ("replicas", "<u4"), ("status", "<i4"),
+])
 STATE_FIELDS = ("log_end_offset", "log_end_pos", "log_start_offset", "log_start_pos", "commit",
                 "high_watermark", "term", "term_start", "leader_commit", "last_log_term", "voted_term",
                 "voted_for", "led", "heard_round")
@@ -558,6 +562,21 @@ class Engine:
         if rc not in (A.RMQ_OK, A.RMQ_ECORRUPT):
             raise EngineError(rc, "rmq_scrub")
         self.last_scrub_rc = rc
+        return out
+
+    def repair(self, first: int = 0, n: int | None = None, dry_run: bool = False) -> np.ndarray:
+        """rmq_repair: scrub partitions [first, first + n), rewrite every (local slot, segment) pair
+        that fails from the lowest local slot on which that segment passes, and scrub again
+        (FORMAT.md §10, "Repair"): a structured array of rmq_repair_res, one row per partition.
+        dry_run counts what would be rewritten and writes nothing. What remains raises nothing (the
+        rows say where it is); self.last_repair_rc keeps the call's return value, RMQ_OK or
+        RMQ_ECORRUPT. Drains first (collective with a transport)."""
+        n = self.cfg.num_partitions - first if n is None else n
+        out = np.zeros(max(n, 0), REPAIR_RES_DTYPE)
+        rc = self.lib.rmq_repair(self.h, first, n, A.RMQ_REPAIR_DRY_RUN if dry_run else 0, _ptr(out) if n else None)
+        if rc not in (A.RMQ_OK, A.RMQ_ECORRUPT):
+            raise EngineError(rc, "rmq_repair")
+        self.last_repair_rc = rc
         return out
 
     def fault_flip_ring(self, replica: int, pidx: int, ring_off: int, xor_mask: int = 0x5A) -> None:

@@ -181,10 +181,16 @@ class PartitionBroker:
 
     def __init__(self, directory: PartitionDirectory, engine=None, *, replication_factor: int = 1,
                  segment_bytes: int = 1 << 22, index_interval: int = 4096, device: int = 0,
-                 messages_as_str: bool = True, durable=None, verify: bool = False):
+                 messages_as_str: bool = True, durable=None, verify: bool = False,
+                 repair: bool = False):
         """verify: reads carry RMQ_FETCH_VERIFY, and a slice with a record that fails its CRC32C or
         framing is answered by a failed MessageBatchReadResponse (no messages, the offset the
         consumer stands at, an error message) instead of being served. Off by default.
+        repair: only meaningful together with verify. A read refused with RMQ_ECORRUPT calls
+        ``engine.repair(p, 1)`` once for each such partition (FORMAT.md §10, "Repair"), and the
+        refused requests are fetched again, verified: those that now pass are served normally, the
+        others get the failed response above. For engines without a transport only: with one,
+        rmq_repair is collective, and a read processor cannot make every rank call it. Off by default.
         durable: a ``ripplemq_amd.tier.DurableLog`` over this engine, or None. With it, a read
         below a ring's retained start is served from the segment files (the reference never
         evicts, PartitionStateMachine.java:26) instead of failing with RMQ_EOFFSET."""
@@ -198,6 +204,7 @@ class PartitionBroker:
         self.engine = engine
         self.as_str = messages_as_str
         self.verify = bool(verify)
+        self.repair = bool(repair)
         self._sms: dict[str, PartitionStateMachine] = {}
 
     def close(self) -> None:
@@ -316,8 +323,20 @@ class PartitionBroker:
         if idx:
             _, res, buf, _ = self.engine.fetch(np.asarray(p, np.uint32), np.asarray(c, np.uint32),
                                                np.asarray(mx, np.uint32), **({"verify": True} if self.verify else {}))
+            rows = [(res, buf, k) for k in range(len(idx))]
+            bad = [k for k in range(len(idx)) if int(res["status"][k]) == A.RMQ_ECORRUPT]
+            if bad and self.verify and self.repair:
+                # heal the refused partitions from their clean local replicas, then read those again
+                for pi in sorted({p[k] for k in bad}):
+                    self.engine.repair(pi, 1)
+                _, res2, buf2, _ = self.engine.fetch(np.asarray([p[k] for k in bad], np.uint32),
+                                                     np.asarray([c[k] for k in bad], np.uint32),
+                                                     np.asarray([mx[k] for k in bad], np.uint32), verify=True)
+                for j, k in enumerate(bad):
+                    rows[k] = (res2, buf2, j)
             spilled = False
-            for k, r in enumerate(idx):
+            for kk, r in enumerate(idx):
+                res, buf, k = rows[kk]
                 st = int(res["status"][k])
                 if st == A.RMQ_ENOTLEADER:
                     out[r] = NOT_LEADER
@@ -330,9 +349,9 @@ class PartitionBroker:
                         spilled = True
                     # (the row's start_offset is the first retained offset there: the consumer's
                     # own offset comes from the table)
-                    off = int(self.engine.consumer_offsets(p[k])[c[k]])
-                    hw = int(self.engine.state(p[k])["high_watermark"])
-                    recs = self.durable.read(p[k], off, min(mx[k], hw - off))
+                    off = int(self.engine.consumer_offsets(p[kk])[c[kk]])
+                    hw = int(self.engine.state(p[kk])["high_watermark"])
+                    recs = self.durable.read(p[kk], off, min(mx[kk], hw - off))
                     out[r] = MessageBatchReadResponse([_decode(b, self.as_str) for _, _, b in recs], off)
                     continue
                 if st == A.RMQ_ECORRUPT:  # (only under verify: the slice failed its checks, nothing is served)

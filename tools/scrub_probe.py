@@ -3,7 +3,11 @@
 rmq_profile_enable (kernel 2: an event before the plan kernel to one after the verify kernel), and
 prints ONE JSON line: bytes scanned, records, kernel-2 ms, GB/s and the fraction of the HBM peak
 bench.py uses; then the fetch kernels' region (kernel 4) at max = 10 and max = 1024 with and
-without RMQ_FETCH_VERIFY.
+without RMQ_FETCH_VERIFY. The repair leg (rmq_repair, kernel 5: an event before its first kernel to one
+after its last) runs on the same state in the same process: on the clean logs, beside the scrub,
+and after slot 1 of every tenth partition was damaged in every segment of its retained log (one
+byte flipped per segment with rmq_fault_flip_ring, the first byte of the segment's first header),
+so every segment of those slots is rewritten from slot 0.
 
     python tools/scrub_probe.py [--batches 192] [--reps 5]
 """
@@ -20,6 +24,53 @@ from ripplemq_amd.engine import Engine, EngineConfig  # noqa: E402
 from ripplemq_amd.workload import CONFIGS, make_batch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak: the constant of bench.py
+
+
+def repair_leg(eng, cfg, st, reps, scrub_ms) -> dict:
+    P, S, I = cfg.num_partitions, cfg.segment_bytes, cfg.index_interval
+    ts = []
+    for _ in range(reps + 1):  # clean logs: the first pass alone
+        eng.profile(1)
+        rows = eng.repair()
+        n, t = eng.profile_query(5)
+        eng.profile(0)
+        assert n == 1 and eng.last_repair_rc == A.RMQ_OK and not rows["segments_repaired"].any()
+        ts.append(t)
+    ts = sorted(ts[1:])
+    out = {"clean_kernel5_ms": {"median": ts[len(ts) // 2], "min": ts[0], "max": ts[-1], "reps": len(ts)},
+           "clean_minus_scrub_ms": ts[len(ts) // 2] - scrub_ms[len(scrub_ms) // 2],
+           "scrub_spread_ms": scrub_ms[-1] - scrub_ms[0]}
+    # slot 1 of every tenth partition: one flip at the start of every non-empty segment
+    flips, nbytes = [], 0
+    for p in range(0, P, 10):
+        sp, ep = int(st["log_start_pos"][p]), int(st["log_end_pos"][p])
+        lo, hi = (sp + I - 1) // I, ep // I
+        cuts = [sp] + ([int(x) for x in eng.read_index(p, lo, hi - lo + 1)[:, 1]] if lo <= hi else []) + [ep]
+        for a, b in zip(cuts, cuts[1:]):
+            if b > a:
+                flips.append((p, a % S))
+                nbytes += b - a
+    ts = []
+    for _ in range(reps + 1):
+        for p, off in flips:
+            eng.fault_flip_ring(1, p, off)
+        eng.profile(1)
+        rows = eng.repair()
+        n, t = eng.profile_query(5)
+        eng.profile(0)
+        assert n == 1 and eng.last_repair_rc == A.RMQ_OK and not rows["segments_unrepaired"].any()
+        assert (int(rows["segments_repaired"].sum()), int(rows["bytes_repaired"].sum())) == (len(flips), nbytes)
+        ts.append(t)
+    ts = sorted(ts[1:])
+    med = ts[len(ts) // 2]
+    clean = out["clean_kernel5_ms"]["median"]
+    out.update({"damaged_partitions": len(range(0, P, 10)), "segments_rewritten": len(flips), "bytes_rewritten": nbytes,
+                "damaged_kernel5_ms": {"median": med, "min": ts[0], "max": ts[-1], "reps": len(ts)},
+                # two audits (about twice the clean call) and the copy between them
+                "rewrite_gbs_whole_call": nbytes / (med * 1e-3) / 1e9,
+                "rewrite_gbs_copy_alone": nbytes / (max(med - 2 * clean, 1e-6) * 1e-3) / 1e9})
+    assert eng.scrub() is not None and eng.last_scrub_rc == A.RMQ_OK
+    return out
 
 
 def main() -> None:
@@ -58,6 +109,7 @@ def main() -> None:
                 "kernel2_ms": {"median": med, "min": ms[0], "max": ms[-1], "reps": len(ms)},
                 "gbs": scanned / (med * 1e-3) / 1e9, "hbm_peak_gbs": HBM_PEAK_GBS,
                 "hbm_frac": scanned / (med * 1e-3) / 1e9 / HBM_PEAK_GBS}
+        line["repair"] = repair_leg(eng, cfg, st, args.reps, ms)
         # the fetch kernels with and without the flag: every consumer at its log start
         pp = np.repeat(np.arange(P, dtype=np.uint32), 4)
         cc = np.tile(np.arange(4, dtype=np.uint32), P)
