@@ -488,6 +488,48 @@ typedef struct rmq_repair_res {
    repairs only the slots it holds. */
 int rmq_repair(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags, rmq_repair_res* res);
 
+/* ---- remote repair (added after ABI 11 without a bump, as rmq_repair was: one struct and two
+   functions, nothing existing moves) ---- */
+typedef struct rmq_repair_remote_res {
+  uint64_t segments_repaired;    /* as rmq_repair_res: rewritten from a clean local slot */
+  uint64_t bytes_repaired;
+  uint64_t segments_fetched;     /* failing pairs rewritten with bytes a peer served */
+  uint64_t bytes_fetched;        /* their segment bytes (end - pos of each) */
+  uint64_t segments_unrepaired;  /* failing pairs left as they were after every round */
+  uint64_t bad_offset;           /* what remains AFTER the call, as rmq_scrub_res reports it */
+  uint32_t bad_replica;
+  uint32_t bad_kind;
+  uint32_t replicas;
+  int32_t status;                /* RMQ_OK, or RMQ_ECORRUPT if something remains */
+} rmq_repair_remote_res;         /* 64 bytes */
+/* rmq_repair, then the pairs it had to leave are fetched from the ranks that hold the partition's
+   other replica slots (FORMAT.md §10 "Remote repair"). Pass 0 is rmq_repair's audit and local copy.
+   A pair still failing whose segment has bounds and whose records are all at or below this
+   replica's commit is then asked of one candidate rank per round, RF - 1 rounds: the leader's rank
+   first, then the other slots' ranks by ascending slot. The donor checks every request word against
+   its own state, walks the span in its own ring under the rules of the verified fetch and sends
+   only a span that passes; the requester walks the span again where it arrived and only then copies
+   it into the failing slot's ring, so no unverified byte reaches a ring. What is never written is
+   what rmq_repair never writes; an uncommitted tail is never fetched. The range is then audited
+   again and the rows report what remains. flags: 0 or RMQ_REPAIR_DRY_RUN (the same exchanges,
+   directory-only responses, the counters of the real call, no ring byte changes anywhere); any
+   other bit is RMQ_EINVAL. res (host, [n], nullable); served (nullable, [2]) gets {segments, bytes}
+   this engine sent as a donor. Returns as rmq_repair does. Without a transport the call does
+   exactly what rmq_repair does (segments_fetched = 0, served = {0, 0}). With a transport it is
+   collective: every rank makes it at the same point of its call sequence with the same flags;
+   [first, first + n) is local to each rank, may differ between ranks and only selects which of this
+   rank's partitions are repaired: every rank serves every peer's requests whatever its own range,
+   and a rank with n = 0 still takes part as a donor. Per round and destination at most 65,536 pairs
+   and RMQ_REPAIR_PEER_BYTES (environment, read at rmq_create; default 64 MiB, a capacity and not a
+   tuned number) of segment bytes are asked for; the rest waits for a later round or call. */
+int rmq_repair_remote(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags, rmq_repair_remote_res* res,
+                      uint64_t* served);
+/* Fault injection (tests): the next remote-repair response this engine sends to rank dst has the
+   byte at `at` of its data section XORed with 0x5A (at < 0: counted back from the end of the data
+   section); a response without that byte is sent as it is and uses the flip up. Independent of
+   rmq_fault_corrupt, whose pending flip belongs to the next replication round. Not collective. */
+int rmq_fault_corrupt_repair(rmq_engine* e, uint32_t dst, int64_t at);
+
 /* ---- host utilities ---- */
 /* FORMAT.md §1 records laid back to back in host memory (segment files of a durable tier, fetch
    output): walks them from buf[0], expecting header offsets first, first + 1, ..., and stops at the
@@ -531,7 +573,8 @@ int rmq_host_unregister(rmq_engine* e, void* p);
    RMQ_FETCH_COMMIT or RMQ_FETCH_VERIFY request runs once (each run would commit; the verify
    rewrites the rows). 2: rmq_scrub, an event before its first kernel (the plan) to one after its last
    (the verify), launches = calls. 5: rmq_repair, likewise from before its first kernel to after its
-   last, launches = calls. */
+   last, launches = calls. 6: rmq_repair_remote, from before its first plan to after its last kernel
+   (the exchanges and the host's waits between them included), launches = calls. */
 int rmq_profile_enable(rmq_engine* e, int enable);
 int rmq_profile_query(rmq_engine* e, int kernel, uint64_t* launches, double* total_ms);
 /* Device name / CU count for reports. */

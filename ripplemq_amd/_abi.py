@@ -122,6 +122,14 @@ class RmqRepairRes(C.Structure):
     ]
 
 
+class RmqRepairRemoteRes(C.Structure):
+    _fields_ = [
+        ("segments_repaired", u64), ("bytes_repaired", u64), ("segments_fetched", u64), ("bytes_fetched", u64),
+        ("segments_unrepaired", u64), ("bad_offset", u64), ("bad_replica", u32), ("bad_kind", u32),
+        ("replicas", u32), ("status", i32),
+    ]
+
+
 class RmqAppendStats(C.Structure):
     _fields_ = [
         ("records", u32), ("appended", u32), ("rejected_not_leader", u32),
@@ -188,6 +196,8 @@ _SIGS = {
     "rmq_scrub": (C.c_int, [vp, u32, u32, vp]),
     "rmq_fault_flip_ring": (C.c_int, [vp, u32, u32, u64, u32]),
     "rmq_repair": (C.c_int, [vp, u32, u32, u32, vp]),
+    "rmq_repair_remote": (C.c_int, [vp, u32, u32, u32, vp, C.POINTER(u64)]),
+    "rmq_fault_corrupt_repair": (C.c_int, [vp, u32, C.c_int64]),
     "rmq_scan_records": (C.c_int, [vp, u64, u64, u64, u32, vp, C.POINTER(u64), C.POINTER(u64)]),
     "rmq_tier_append": (C.c_int, [u32, vp, vp, vp, vp, vp, vp, vp, u32, C.c_int]),
 }

@@ -596,6 +596,7 @@ void free_engine(rmq_engine* e) {
                              s.lterm, s.mterm, s.heard, e->d_crc,
                              e->d_stats, e->d_ctl32, e->d_ctl64, e->d_stamps, e->d_rlate, e->d_scrub_tbase, e->d_scrub_rows,
                              e->d_repair_verdict, e->d_repair_counts};
+  repair_remote_free(e);
   if (e->state_stage) hipHostFree(e->state_stage);
   for (rmq_engine::FetchSlot& f : e->fslot) {
     void* fs[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_out};
@@ -789,6 +790,7 @@ int rmq_create(const rmq_config* cfg, rmq_engine** out) {
   if (const char* v = std::getenv("RMQ_VERIFY_WGS")) e->verify_wgs = std::max(1, std::atoi(v));
   if (const char* v = std::getenv("RMQ_BIG_WGS")) e->big_wgs = (uint32_t)std::atoi(v);
   if (const char* v = std::getenv("RMQ_AUDIT_WGS")) e->audit_wgs = (uint32_t)std::max(0, std::atoi(v));
+  if (const char* v = std::getenv("RMQ_REPAIR_PEER_BYTES")) e->repair_peer_bytes = std::strtoull(v, nullptr, 10);
   std::snprintf(e->dev_name, sizeof e->dev_name, "%s (%s)", prop.name, prop.gcnArchName);
   if (e->split && e->rank_cus && e->rank_cus < e->cu_count) {
     // CU masks (bit i = the i-th CU in the runtime's numbering): the rank stream takes the first
@@ -2303,6 +2305,124 @@ int rmq_repair(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags, rmq_re
   return corrupt ? RMQ_ECORRUPT : RMQ_OK;
 }
 
+// rmq_repair's first pass and local copy, then the rounds over the transport (repair_remote.cpp),
+// then the audit again. Without a transport this is rmq_repair step by step.
+int rmq_repair_remote(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags, rmq_repair_remote_res* res,
+                      uint64_t* served) {
+  if (!e || (flags & ~RMQ_REPAIR_DRY_RUN)) return RMQ_EINVAL;
+  EngineLock g(e);
+  if (served) served[0] = served[1] = 0;
+  const uint32_t P = e->cfg.num_partitions, RF = e->cfg.replication_factor;
+  if (first > P || n > P - first) return RMQ_ENOPART;
+  if (!n && !e->repl) return RMQ_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  int rc = drain(e);  // (collective with a transport: a rank with n = 0 drains and serves too)
+  if (rc) return rc;
+  uint64_t tasks = 0;
+  for (uint32_t p = first; p < first + n; ++p)
+    tasks += RF * (((1ull << (e->ring[p] & 63ull)) >> e->st.interval_log2) + 2ull);
+  if (n) {
+    rc = scrub_buffers(e, n);
+    if (rc) return rc;
+    if (e->repair_verdict_cap < tasks) {
+      if (e->d_repair_verdict) hipFree(e->d_repair_verdict);
+      e->d_repair_verdict = nullptr;
+      e->repair_verdict_cap = 0;
+      rc = dalloc(&e->d_repair_verdict, (size_t)tasks);
+      if (rc) return rc;
+      e->repair_verdict_cap = tasks;
+    }
+    if (e->repair_counts_cap < n) {
+      if (e->d_repair_counts) hipFree(e->d_repair_counts);
+      e->d_repair_counts = nullptr;
+      e->repair_counts_cap = 0;
+      rc = dalloc(&e->d_repair_counts, (size_t)n * 3);
+      if (rc) return rc;
+      e->repair_counts_cap = n;
+    }
+  }
+  RepairArgs a{};
+  a.s.st = e->st;
+  a.s.crc = e->d_crc;
+  a.s.tbase = e->d_scrub_tbase;
+  a.s.rows = e->d_scrub_rows;
+  a.s.first = first;
+  a.s.n = n;
+  a.verdict = e->d_repair_verdict;
+  a.counts = e->d_repair_counts;
+  a.write = (flags & RMQ_REPAIR_DRY_RUN) ? 0u : 1u;
+  hipEvent_t r0 = nullptr, r1 = nullptr;
+  if (e->profile) {  // kernel 6: an event before the first plan to one after the last kernel of the call
+    r0 = pool_event(e);
+    r1 = pool_event(e);
+    e->prof[6].push_back({r0, r1});
+    HIP_TRY(hipEventRecord(r0, e->main_s));
+    HIP_TRY(hipEventRecord(r1, e->main_s));  // (recorded again after every later kernel)
+  }
+  std::vector<uint64_t> rows((size_t)n * 4), counts((size_t)n * 3, 0), fetched((size_t)n * 2, 0);
+  bool corrupt = false;
+  if (n) {
+    // pass 0: the scrub with a verdict per task, then rmq_repair's copy from a clean local slot
+    launch_repair_scan(a, audit_wgs(e), e->main_s);
+    HIP_TRY(hipGetLastError());
+    if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
+    rc = stream_wait(e->main_s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(rows.data(), e->d_scrub_rows, rows.size() * 8, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n && !corrupt; ++i) corrupt = rows[4ull * i] != kScrubClean;
+    if (corrupt) {
+      HIP_TRY(hipMemsetAsync(e->d_repair_counts, 0, counts.size() * 8, e->main_s));
+      launch_repair_copy(a, audit_wgs(e), e->main_s);
+      HIP_TRY(hipGetLastError());
+      if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
+    }
+  }
+  uint64_t sv[2] = {0, 0};
+  if (e->repl) {
+    rc = repair_remote_rounds(e, corrupt ? &a : nullptr, audit_wgs(e), tasks, fetched.data(), sv);
+    if (rc) return rc;
+    if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
+  }
+  if (served) served[0] = sv[0], served[1] = sv[1];
+  if (corrupt) {
+    if (a.write) launch_scrub(a.s, audit_wgs(e), e->main_s);
+    HIP_TRY(hipGetLastError());
+    if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
+    rc = stream_wait(e->main_s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(counts.data(), e->d_repair_counts, counts.size() * 8, hipMemcpyDeviceToHost));
+    if (a.write) HIP_TRY(hipMemcpy(rows.data(), e->d_scrub_rows, rows.size() * 8, hipMemcpyDeviceToHost));
+  }
+  corrupt = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t key = rows[4ull * i];
+    corrupt = corrupt || key != kScrubClean;
+    if (!res) continue;
+    rmq_repair_remote_res& x = res[i];
+    std::memset(&x, 0, sizeof x);
+    x.segments_repaired = counts[3ull * i];
+    x.bytes_repaired = counts[3ull * i + 1];
+    x.segments_fetched = fetched[2ull * i];
+    x.bytes_fetched = fetched[2ull * i + 1];
+    x.segments_unrepaired = counts[3ull * i + 2] - fetched[2ull * i];  // (a fetched pair had no local donor)
+    x.replicas = (uint32_t)rows[4ull * i + 3];
+    x.bad_offset = key == kScrubClean ? RMQ_OFFSET_NONE : key >> 5;
+    x.bad_replica = key == kScrubClean ? 0u : (uint32_t)(key >> 2) & 7u;
+    x.bad_kind = key == kScrubClean ? 0u : (uint32_t)key & 3u;
+    x.status = key == kScrubClean ? RMQ_OK : RMQ_ECORRUPT;
+  }
+  return corrupt ? RMQ_ECORRUPT : RMQ_OK;
+}
+
+int rmq_fault_corrupt_repair(rmq_engine* e, uint32_t dst, int64_t at) {
+  if (!e) return RMQ_EINVAL;
+  EngineLock g(e);
+  if (!e->repl || dst >= e->repl->world || dst == e->repl->rank) return RMQ_EINVAL;
+  e->rr.flip[dst] = true;
+  e->rr.flip_at[dst] = at;
+  return RMQ_OK;
+}
+
 int rmq_fault_flip_ring(rmq_engine* e, uint32_t replica, uint32_t p, uint64_t ring_off, uint32_t xor_mask) {
   if (!e) return RMQ_EINVAL;
   EngineLock g(e);
@@ -2380,7 +2500,7 @@ int rmq_profile_enable(rmq_engine* e, int enable) {
 }
 
 int rmq_profile_query(rmq_engine* e, int kernel, uint64_t* launches, double* total_ms) {
-  if (!e || kernel < 0 || kernel > 5) return RMQ_EINVAL;
+  if (!e || kernel < 0 || kernel > 6) return RMQ_EINVAL;
   EngineLock g(e);
   HIP_TRY(hipSetDevice(e->device));
   int rc = settle(e);

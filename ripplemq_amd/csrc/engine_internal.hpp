@@ -1,5 +1,6 @@
 // engine_internal.hpp — the engine object shared by the host-side translation units
-// (engine.cpp: C-ABI, append pipeline, fetch, control; replication.cpp: replica-log rounds).
+// (engine.cpp: C-ABI, append pipeline, fetch, control; replication.cpp: replica-log rounds;
+// repair_remote.cpp: the rounds of rmq_repair_remote).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,6 +33,10 @@ constexpr uint32_t kMaxBatchRecords = kMaxTiles * kTileRecs;       // 524288
 // pipeline scratch sets: a group's set lives from its stage 1 (launch k) to the application of its
 // followers' acks (launch k + 5 with a replication transport), so six sets rotate
 constexpr uint32_t kSets = 6;
+// rmq_repair_remote's control words (rmq_engine::RemoteRepair::words): the words sent [2 * kMaxWorld]
+// and received [2 * kMaxWorld], RemoteReqArgs::ctr [2 * kMaxWorld + 1], RemoteServeArgs::tot [3 * kMaxWorld]
+constexpr uint32_t kRemoteWSend = 0, kRemoteWRecv = 2 * kMaxWorld, kRemoteWCtr = 4 * kMaxWorld,
+                   kRemoteWTot = 6 * kMaxWorld + 1, kRemoteWords = 9 * kMaxWorld + 1;
 
 struct EvPair {
   hipEvent_t a = nullptr, b = nullptr;
@@ -403,14 +408,14 @@ struct rmq_engine {
   uint32_t ctl_cap = 0;
   // profiling: pipeline launches are timed as one region (event before the first launch after
   // enable, event at the next drain) so no per-launch events sit between kernels; fetch kernels
-  // keep per-launch event pairs (prof[3], prof[4]), and so do every rmq_scrub (prof[2]) and every rmq_repair (prof[5])
+  // keep per-launch event pairs (prof[3], prof[4]), and so do every rmq_scrub (prof[2]), every rmq_repair (prof[5]) and every rmq_repair_remote (prof[6])
   uint32_t profile = 0;
   uint32_t fetch_replay = 1;     // rmq_profile_enable(k >= 2): each fetch's kernels run k times
   uint64_t prof_fetch_runs = 0;
   uint64_t prof_launches = 0, prof_batches = 0;
   hipEvent_t prof_t0 = nullptr, prof_t1 = nullptr;
   bool prof_started = false, prof_ended = false;
-  std::vector<EvPair> prof[6];
+  std::vector<EvPair> prof[7];
   // rmq_scrub: the plan's scan and the result rows of the partitions of one call (grown on demand)
   uint64_t* d_scrub_tbase = nullptr;
   uint64_t* d_scrub_rows = nullptr;
@@ -420,6 +425,29 @@ struct rmq_engine {
   uint64_t repair_verdict_cap = 0;
   uint64_t* d_repair_counts = nullptr;
   uint32_t repair_counts_cap = 0;
+  // rmq_repair_remote (repair_remote.cpp): device buffers grown on demand (a capacity next to each),
+  // fixed control words with their page-locked mirror, the per-destination budget and the fault hook
+  struct RemoteRepair {
+    uint8_t* want = nullptr;     // [tasks] RemoteReqArgs::want
+    uint64_t* fetched = nullptr; // [n][2]
+    uint32_t* cand = nullptr;    // [n][RF - 1]
+    uint64_t* pkey = nullptr;    // [P]
+    RemoteKey* keys = nullptr;   // [P]
+    uint8_t* lists = nullptr;    // request lists, one per destination
+    uint8_t* rin = nullptr;      // request lists received
+    uint64_t* sv = nullptr;      // [requests received]
+    uint8_t* out = nullptr;      // responses
+    uint8_t* in = nullptr;       // responses received
+    uint64_t want_cap = 0, fetched_cap = 0, cand_cap = 0, key_cap = 0, lists_cap = 0, rin_cap = 0, sv_cap = 0,
+             out_cap = 0, in_cap = 0;
+    uint64_t* csum = nullptr;    // [kMaxWorld][kRemoteChunks]
+    uint64_t* words = nullptr;   // [kRemoteWords] exchanged words, counters and totals
+    uint64_t* h_words = nullptr; // pinned mirror, then the list headers
+    hipEvent_t ev = nullptr;
+    bool flip[kMaxWorld] = {};   // rmq_fault_corrupt_repair: the next response to q
+    int64_t flip_at[kMaxWorld] = {};
+  } rr;
+  uint64_t repair_peer_bytes = 64ull << 20;  // RMQ_REPAIR_PEER_BYTES: segment bytes asked of one rank per round (a capacity)
   std::vector<hipEvent_t> ev_pool;
   // diagnostics: RMQ_STAMPS=<csv> records per-wave phase stamps of launch RMQ_STAMPS_AT (default 100)
   const char* stamps_path = nullptr;
@@ -511,5 +539,13 @@ int repl_before_launch(rmq_engine* e, PipeArgs& a);
 int repl_after_launch(rmq_engine* e, const GroupFlight* s2, const GroupFlight* s3);
 int repl_drain(rmq_engine* e);
 int reset_catchup(rmq_engine* e);
+// repair_remote.cpp
+// The rounds of rmq_repair_remote (FORMAT.md §10 "Remote repair") after the first pass, engine
+// drained, transport attached. a: the first pass's plan and verdicts with something still failing,
+// or null (nothing to ask for: this rank only serves); wgs: the request kernel's grid;
+// tasks: the verdicts' capacity; fetched: [n][2] host {pairs, bytes} (a != null); served: [2].
+int repair_remote_rounds(rmq_engine* e, const RepairArgs* a, uint32_t wgs, uint64_t tasks, uint64_t* fetched,
+                         uint64_t* served);
+void repair_remote_free(rmq_engine* e);
 
 }  // namespace rmq

@@ -474,6 +474,65 @@ struct RepairArgs {
   uint32_t write;     // 0: count only (RMQ_REPAIR_DRY_RUN)
 };
 
+// rmq_repair_remote (repair_remote.hip, FORMAT.md §10 "Remote repair"): the wire sizes, and the
+// arguments of the request, serve and install kernels of one round.
+constexpr uint32_t kRemoteMagic = 0x31525152u;  // "RQR1": request list and response headers
+constexpr uint32_t kRemoteHdr = 16;      // header bytes of a request list and of a response
+constexpr uint32_t kRemoteReq = 48;      // request bytes {key, pos, end, expect, eoff, cookie}
+constexpr uint32_t kRemoteDir = 16;      // response directory entry bytes {cookie, status, data_start / 16}
+constexpr uint32_t kRemoteMaxReqs = 1u << 16;  // pairs asked of one destination in one round
+constexpr uint32_t kRemoteChunk = 256;   // requests per chunk sum of the serve's placement
+constexpr uint32_t kRemoteChunks = kRemoteMaxReqs / kRemoteChunk;  // chunk sums per source
+constexpr uint32_t kRemoteDry = 1u;      // request list header flag: answer with the directory only
+constexpr uint32_t kRemoteServed = 0u, kRemoteUnknown = 1u, kRemoteOutside = 2u, kRemoteBadWalk = 3u;
+struct RemoteKey {    // the donor's sorted {placement key, local pidx} table
+  uint64_t key;
+  uint32_t pidx, pad;
+};
+// Requester, before a round's exchanges: the pairs still wanted go into the list of the round's
+// candidate rank.
+struct RemoteReqArgs {
+  RepairArgs r;             // the plan, the verdicts and the counters of the first pass
+  uint8_t* want;            // [tasks] 1: the pair failed with no passing local slot and is not installed yet
+                            //   (round 0 writes every byte, the install clears the ones it heals)
+  const uint32_t* cand;     // [n][ncand] donor candidate ranks of each partition of the range, ~0: none
+  const uint64_t* pkey;     // [P] placement keys
+  uint8_t* lists;           // destination d's request list at d * list_cap
+  uint64_t list_cap;        // bytes of one list (kRemoteHdr + max_reqs requests)
+  uint64_t* ctr;            // [2 * world + 1] {requests appended per destination (may pass max_reqs),
+                            //   segment bytes asked of it, pairs that want a candidate this round}
+  uint64_t peer_bytes;      // segment bytes asked of one destination at most (RMQ_REPAIR_PEER_BYTES)
+  uint32_t round, world, ncand, max_reqs;
+};
+// Donor: the request lists received from every source, one wave per request.
+struct RemoteServeArgs {
+  DevState st;
+  const CrcConsts* crc;
+  const RemoteKey* keys;    // [nkeys] ascending by key
+  uint32_t nkeys, world;
+  const uint8_t* in;        // received lists
+  uint64_t in_off[kMaxWorld];   // byte offset of source q's list in `in`
+  uint32_t w0[kMaxWorld + 1];   // prefix of the sources' request counts (host: from the bytes received)
+  uint64_t* sv;             // [w0[world]] check -> copy: span bytes | local slot << 48 | status << 60
+  uint64_t* csum;           // [world][kRemoteChunks] data bytes of each chunk of kRemoteChunk requests
+  uint64_t* tot;            // [world][3] {spans served, their bytes, data bytes (0 for a dry list)}
+  uint8_t* out;             // responses
+  uint64_t out_off[kMaxWorld];  // byte offset of source q's response in `out`
+};
+// Requester, after a round's responses: one wave per directory entry.
+struct RemoteInstallArgs {
+  RepairArgs r;
+  uint8_t* want;
+  const uint8_t* lists;     // the request lists as sent
+  uint64_t list_cap;
+  uint32_t w0[kMaxWorld + 1];   // prefix of the requests sent to each rank this round
+  const uint8_t* in;        // received responses
+  uint64_t in_off[kMaxWorld];
+  uint64_t in_bytes[kMaxWorld]; // bytes received from each rank
+  uint64_t* fetched;        // [n][2] {pairs fetched, their segment bytes}
+  uint32_t world, pad;
+};
+
 // launchers (defined in the .hip files)
 // start: an event the dispatch records as the kernel starts (profiling), or null
 void launch_pipeline(const PipeArgs& a, hipStream_t s, hipEvent_t start = nullptr);
@@ -504,6 +563,10 @@ void launch_scrub(const ScrubArgs& a, uint32_t verify_wgs, hipStream_t s);  // p
 void launch_scrub_plan(const ScrubArgs& a, hipStream_t s);
 void launch_repair_scan(const RepairArgs& a, uint32_t wgs, hipStream_t s);  // plan, then verify with verdicts
 void launch_repair_copy(const RepairArgs& a, uint32_t wgs, hipStream_t s);
+void launch_remote_request(const RemoteReqArgs& a, uint32_t wgs, hipStream_t s);
+void launch_remote_serve_check(const RemoteServeArgs& a, hipStream_t s);  // a wave per request: verdict and span bytes
+void launch_remote_serve_copy(const RemoteServeArgs& a, hipStream_t s);   // header, directory, passing spans
+void launch_remote_install(const RemoteInstallArgs& a, hipStream_t s);
 
 }  // namespace rmq
 

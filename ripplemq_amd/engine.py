@@ -66,6 +66,11 @@ REPAIR_RES_DTYPE = np.dtype([
     ("segments_repaired", "<u8"), ("bytes_repaired", "<u8"), ("segments_unrepaired", "<u8"),
     ("bad_offset", "<u8"), ("bad_replica", "<u4"), ("bad_kind", "<u4"), ("replicas", "<u4"), ("status", "<i4"),
 ])
+REPAIR_REMOTE_RES_DTYPE = np.dtype([
+    ("segments_repaired", "<u8"), ("bytes_repaired", "<u8"), ("segments_fetched", "<u8"), ("bytes_fetched", "<u8"),
+    ("segments_unrepaired", "<u8"), ("bad_offset", "<u8"), ("bad_replica", "<u4"), ("bad_kind", "<u4"),
+    ("replicas", "<u4"), ("status", "<i4"),
+])
 STATE_FIELDS = ("log_end_offset", "log_end_pos", "log_start_offset", "log_start_pos", "commit",
                 "high_watermark", "term", "term_start", "leader_commit", "last_log_term", "voted_term",
                 "voted_for", "led", "heard_round")
@@ -578,6 +583,29 @@ class Engine:
             raise EngineError(rc, "rmq_repair")
         self.last_repair_rc = rc
         return out
+
+    def repair_remote(self, first: int = 0, n: int | None = None, dry_run: bool = False) -> np.ndarray:
+        """rmq_repair_remote: repair(), then the pairs it had to leave are fetched from the ranks that
+        hold the partition's other replica slots and installed once they verify here (FORMAT.md §10,
+        "Remote repair"): a structured array of rmq_repair_remote_res, one row per partition.
+        self.last_repair_rc keeps the return value (RMQ_OK or RMQ_ECORRUPT), self.last_repair_served
+        the (segments, bytes) this engine sent as a donor. Without a transport it is repair(). With
+        one it is collective: every rank calls it, with its own range (n = 0: a donor only)."""
+        n = self.cfg.num_partitions - first if n is None else n
+        out = np.zeros(max(n, 0), REPAIR_REMOTE_RES_DTYPE)
+        served = (C.c_uint64 * 2)()
+        rc = self.lib.rmq_repair_remote(self.h, first, n, A.RMQ_REPAIR_DRY_RUN if dry_run else 0,
+                                        _ptr(out) if n else None, served)
+        if rc not in (A.RMQ_OK, A.RMQ_ECORRUPT):
+            raise EngineError(rc, "rmq_repair_remote")
+        self.last_repair_rc = rc
+        self.last_repair_served = (int(served[0]), int(served[1]))
+        return out
+
+    def fault_corrupt_repair(self, dst: int, at: int) -> None:
+        """Tests: the next remote-repair response sent to dst has one data byte flipped
+        (rmq_fault_corrupt_repair)."""
+        _check(self.lib.rmq_fault_corrupt_repair(self.h, dst, at), "rmq_fault_corrupt_repair")
 
     def fault_flip_ring(self, replica: int, pidx: int, ring_off: int, xor_mask: int = 0x5A) -> None:
         """Tests: XOR one byte of a local replica ring (rmq_fault_flip_ring), addressed as
