@@ -530,6 +530,56 @@ int rmq_repair_remote(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags,
    rmq_fault_corrupt, whose pending flip belongs to the next replication round. Not collective. */
 int rmq_fault_corrupt_repair(rmq_engine* e, uint32_t dst, int64_t at);
 
+/* ---- restore (added after ABI 11 without a bump, as the repairs were: two structs, one flag and
+   one function, nothing existing moves) ---- */
+#define RMQ_RESTORE_DRY_RUN 1u          /* verify and report, write nothing */
+typedef struct rmq_restore_item {        /* 64 bytes */
+  uint32_t pidx;
+  uint32_t flags;        /* 0 */
+  uint64_t first_offset; /* header offset of the run's first record = the new log_start_offset */
+  uint64_t first_pos;    /* logical position it takes = the new log_start_pos; multiple of 16 */
+  uint64_t count;        /* records in the run */
+  uint64_t bytes;        /* run bytes; the run is buf[buf_pos, buf_pos + bytes) */
+  uint64_t buf_pos;      /* multiple of 16 */
+  uint64_t table_start;  /* rec_pos[table_start + k], k in [0, count]: record k's byte position inside
+                            the run, then the run's end (== bytes): what rmq_scan_records /
+                            rmq_tier_append write as pos_out */
+  uint64_t commit;       /* the replica's commit after the restore, in [first_offset, first_offset + count] */
+} rmq_restore_item;
+typedef struct rmq_restore_res {         /* 32 bytes */
+  uint64_t records;      /* records installed (dry run: that would be) */
+  uint64_t bytes;
+  uint64_t bad_offset;   /* lowest expected offset of a failing record; RMQ_OFFSET_NONE if none */
+  uint32_t bad_kind;     /* RMQ_SCRUB_BAD_CRC / RMQ_SCRUB_BAD_CHAIN */
+  int32_t status;        /* RMQ_OK, RMQ_ECORRUPT, RMQ_EINVAL, RMQ_ENOSPC, RMQ_ENOPART */
+} rmq_restore_res;
+/* Loads replica logs from FORMAT.md §1 record images (segment files of a durable tier) on the device
+   (FORMAT.md §11 "Restore"). Item i restarts the pristine partition items[i].pidx (log start and end
+   offsets and positions all 0) as the log [first_offset, first_offset + count) at logical positions
+   [first_pos, first_pos + bytes), from the run buf[buf_pos, buf_pos + bytes) and its record
+   positions rec_pos[table_start .. table_start + count]. items, rec_pos (rec_words words) and res
+   ([n], nullable) are host arrays; buf (buf_bytes bytes, 16-byte aligned) is RMQ_MEM_HOST or
+   RMQ_MEM_DEVICE; a host buffer and the table go to device scratch the engine keeps (RMQ_ENOMEM,
+   nothing changed, if it cannot be allocated). A row that fails the host checks (RMQ_ENOPART,
+   RMQ_ENOSPC: bytes over the ring, RMQ_EINVAL: alignment, ranges, counts, commit, flags, a partition
+   that is not pristine, named twice or without a local slot) is skipped and the others proceed. On
+   the device every record is verified first, a lane per record: the table tiles the run, header
+   offsets run first_offset + k, each record's size is the distance to the next table word, CRC32C
+   and zero padding; no table or length word is an address before these hold. A partition with any
+   failing record gets RMQ_ECORRUPT with the lowest failing expected offset and its kind and stays
+   pristine in every respect. A partition that passes is installed: the run into every local replica
+   slot's ring at pos mod S_p, the sparse index entries of §5, log start (first_offset, first_pos),
+   log end, commit = high_watermark = leader_commit = item.commit, match of the local slots = the log
+   end and of the others 0, both state sets, its position-cache entries emptied. Terms, votes,
+   leadership and consumer offsets are not touched (rmq_become_leader, rmq_set_vote,
+   rmq_commit_consumer_offset restore them). flags: 0 or RMQ_RESTORE_DRY_RUN (the rows of the real
+   call, nothing written); any other bit is RMQ_EINVAL, and so are a null engine, null items with
+   n != 0, an unknown mem and an attached transport (a restarted rank restores before it attaches).
+   Returns RMQ_OK if every row is, else the status of the lowest-index row that is not. Drains first. */
+int rmq_restore(rmq_engine* e, uint32_t n, const rmq_restore_item* items, uint32_t mem,
+                const uint8_t* buf, uint64_t buf_bytes, const uint64_t* rec_pos, uint64_t rec_words,
+                uint32_t flags, rmq_restore_res* res);
+
 /* ---- host utilities ---- */
 /* FORMAT.md §1 records laid back to back in host memory (segment files of a durable tier, fetch
    output): walks them from buf[0], expecting header offsets first, first + 1, ..., and stops at the
@@ -574,7 +624,9 @@ int rmq_host_unregister(rmq_engine* e, void* p);
    rewrites the rows). 2: rmq_scrub, an event before its first kernel (the plan) to one after its last
    (the verify), launches = calls. 5: rmq_repair, likewise from before its first kernel to after its
    last, launches = calls. 6: rmq_repair_remote, from before its first plan to after its last kernel
-   (the exchanges and the host's waits between them included), launches = calls. */
+   (the exchanges and the host's waits between them included), launches = calls. 7: rmq_restore, an
+   event before its first kernel to one after its last (the staging copies before them outside),
+   launches = calls. */
 int rmq_profile_enable(rmq_engine* e, int enable);
 int rmq_profile_query(rmq_engine* e, int kernel, uint64_t* launches, double* total_ms);
 /* Device name / CU count for reports. */

@@ -30,6 +30,7 @@ RMQ_SCAN_CHECK = 1
 RMQ_SCRUB_BAD_CRC = 1
 RMQ_SCRUB_BAD_CHAIN = 2
 RMQ_REPAIR_DRY_RUN = 1
+RMQ_RESTORE_DRY_RUN = 1
 
 RMQ_OK = 0
 RMQ_PENDING = 1
@@ -130,6 +131,17 @@ class RmqRepairRemoteRes(C.Structure):
     ]
 
 
+class RmqRestoreItem(C.Structure):
+    _fields_ = [
+        ("pidx", u32), ("flags", u32), ("first_offset", u64), ("first_pos", u64), ("count", u64), ("bytes", u64),
+        ("buf_pos", u64), ("table_start", u64), ("commit", u64),
+    ]
+
+
+class RmqRestoreRes(C.Structure):
+    _fields_ = [("records", u64), ("bytes", u64), ("bad_offset", u64), ("bad_kind", u32), ("status", i32)]
+
+
 class RmqAppendStats(C.Structure):
     _fields_ = [
         ("records", u32), ("appended", u32), ("rejected_not_leader", u32),
@@ -198,6 +210,7 @@ _SIGS = {
     "rmq_repair": (C.c_int, [vp, u32, u32, u32, vp]),
     "rmq_repair_remote": (C.c_int, [vp, u32, u32, u32, vp, C.POINTER(u64)]),
     "rmq_fault_corrupt_repair": (C.c_int, [vp, u32, C.c_int64]),
+    "rmq_restore": (C.c_int, [vp, u32, vp, u32, vp, u64, vp, u64, u32, vp]),
     "rmq_scan_records": (C.c_int, [vp, u64, u64, u64, u32, vp, C.POINTER(u64), C.POINTER(u64)]),
     "rmq_tier_append": (C.c_int, [u32, vp, vp, vp, vp, vp, vp, vp, u32, C.c_int]),
 }

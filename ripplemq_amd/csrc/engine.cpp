@@ -14,6 +14,7 @@
 #include <chrono>
 
 #include "engine_internal.hpp"
+#include "restore_check.hpp"
 
 using namespace rmq;
 
@@ -595,7 +596,8 @@ void free_engine(rmq_engine* e) {
                              s.local_mask, s.index, s.logs, s.ring, s.cons, s.pcache, s.rcur, s.cdirty, s.lcommit, s.csnap, s.cver, s.cq,
                              s.lterm, s.mterm, s.heard, e->d_crc,
                              e->d_stats, e->d_ctl32, e->d_ctl64, e->d_stamps, e->d_rlate, e->d_scrub_tbase, e->d_scrub_rows,
-                             e->d_repair_verdict, e->d_repair_counts};
+                             e->d_repair_verdict, e->d_repair_counts, e->rs.buf, e->rs.tab, e->rs.items, e->rs.rbase,
+                             e->rs.key};
   repair_remote_free(e);
   if (e->state_stage) hipHostFree(e->state_stage);
   for (rmq_engine::FetchSlot& f : e->fslot) {
@@ -2414,6 +2416,116 @@ int rmq_repair_remote(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags,
   return corrupt ? RMQ_ECORRUPT : RMQ_OK;
 }
 
+// Host checks (restore_check.hpp), staging, then verify -> install -> finish on the pipeline stream
+// (restore.hip): the verdicts stay on the device between the passes and are read back once.
+int rmq_restore(rmq_engine* e, uint32_t n, const rmq_restore_item* items, uint32_t mem, const uint8_t* buf,
+                uint64_t buf_bytes, const uint64_t* rec_pos, uint64_t rec_words, uint32_t flags, rmq_restore_res* res) {
+  if (!e || (flags & ~RMQ_RESTORE_DRY_RUN) || (n && !items) || (mem != RMQ_MEM_HOST && mem != RMQ_MEM_DEVICE) ||
+      (buf_bytes && !buf) || (rec_words && !rec_pos) || (mem == RMQ_MEM_DEVICE && ((uintptr_t)buf & 15u)))
+    return RMQ_EINVAL;
+  EngineLock g(e);
+  if (e->repl) return RMQ_EINVAL;  // a restarted rank restores before it attaches
+  if (!n) return RMQ_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  int rc = drain(e);
+  if (rc) return rc;
+  const uint32_t P = e->cfg.num_partitions, RF = e->cfg.replication_factor;
+  // pristine: log start and end offsets and positions all 0 (the engine is drained: the current set)
+  std::vector<uint64_t> so(P), sp(P), eo(P), ep(P);
+  HIP_TRY(hipMemcpy(so.data(), e->st.start_off, (size_t)P * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(sp.data(), e->st.start_pos, (size_t)P * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(eo.data(), e->st.leo, (size_t)P * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ep.data(), e->st.used, (size_t)P * 8, hipMemcpyDeviceToHost));
+  const RestorePlan pl = restore_plan(n, items, P, buf_bytes, rec_words, [&](uint32_t p) {
+    RestorePart q;
+    q.seg = 1ull << (e->ring[p] & 63ull);
+    q.pristine = !(so[p] | sp[p] | eo[p] | ep[p]);
+    q.local = false;
+    for (uint32_t r = 0; r < RF; ++r) q.local = q.local || e->ranks[(size_t)p * RF + r] == e->cfg.rank;
+    return q;
+  });
+  const uint32_t na = (uint32_t)pl.accepted.size();
+  std::vector<uint64_t> key(na, kScrubClean);
+  if (na) {
+    const bool host = mem == RMQ_MEM_HOST;
+    rmq_engine::Restore& B = e->rs;
+    if (B.items_cap < na) {  // the three per-item arrays share a capacity
+      uint64_t c0 = 0, c1 = 0, c2 = 0;
+      B.items_cap = 0;
+      rc = restore_grow(&B.items, &c0, na);
+      if (!rc) rc = restore_grow(&B.rbase, &c1, (uint64_t)na + 1);
+      if (!rc) rc = restore_grow(&B.key, &c2, na);
+      if (!rc) B.items_cap = na;
+    }
+    if (!rc) rc = restore_grow(&B.tab, &B.tab_cap, pl.tab_hi - pl.tab_lo);
+    if (!rc && host && pl.buf_hi > pl.buf_lo) rc = restore_grow(&B.buf, &B.buf_cap, pl.buf_hi - pl.buf_lo);
+    if (rc) return rc;
+    std::vector<RestoreItem> di(na);
+    for (uint32_t k = 0; k < na; ++k) {
+      const rmq_restore_item& it = items[pl.accepted[k]];
+      RestoreItem& d = di[k];
+      d.first_off = it.first_offset, d.first_pos = it.first_pos, d.count = it.count, d.bytes = it.bytes;
+      d.run = host ? B.buf + (it.bytes ? it.buf_pos - pl.buf_lo : 0ull) : buf + it.buf_pos;
+      d.tab = B.tab + (it.table_start - pl.tab_lo);
+      d.commit = it.commit;
+      d.pidx = it.pidx, d.pad = 0;
+    }
+    hipStream_t s = e->main_s;
+    HIP_TRY(hipMemcpyAsync(B.items, di.data(), (size_t)na * sizeof(RestoreItem), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(B.rbase, pl.rbase.data(), ((size_t)na + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(B.key, key.data(), (size_t)na * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(B.tab, rec_pos + pl.tab_lo, (size_t)(pl.tab_hi - pl.tab_lo) * 8, hipMemcpyHostToDevice, s));
+    if (host && pl.buf_hi > pl.buf_lo)
+      HIP_TRY(hipMemcpyAsync(B.buf, buf + pl.buf_lo, (size_t)(pl.buf_hi - pl.buf_lo), hipMemcpyHostToDevice, s));
+    RestoreArgs a{};
+    a.st = e->st;
+    a.sets[0] = e->sets[0];
+    a.sets[1] = e->sets[1];
+    a.crc = e->d_crc;
+    a.items = B.items;
+    a.rbase = B.rbase;
+    a.key = B.key;
+    a.n = na;
+    hipEvent_t r0 = nullptr, r1 = nullptr;
+    if (e->profile) {  // kernel 7: an event before the verify to one after the last kernel of the call
+      r0 = pool_event(e);
+      r1 = pool_event(e);
+      e->prof[7].push_back({r0, r1});
+      HIP_TRY(hipEventRecord(r0, s));
+    }
+    const uint64_t records = pl.rbase.back();
+    launch_restore_verify(a, records, audit_wgs(e), s);
+    if (!(flags & RMQ_RESTORE_DRY_RUN)) launch_restore_install(a, records, audit_wgs(e), s);
+    HIP_TRY(hipGetLastError());
+    if (e->profile) HIP_TRY(hipEventRecord(r1, s));
+    HIP_TRY(hipMemcpyAsync(key.data(), B.key, (size_t)na * 8, hipMemcpyDeviceToHost, s));
+    rc = stream_wait(s);  // (the caller's buffers are free again, and the rows can be written)
+    if (rc) return rc;
+  }
+  std::vector<int32_t> status = pl.status;
+  for (uint32_t k = 0; k < na; ++k)
+    if (key[k] != kScrubClean) status[pl.accepted[k]] = RMQ_ECORRUPT;
+  if (res) {
+    for (uint32_t i = 0; i < n; ++i) {
+      rmq_restore_res& x = res[i];
+      std::memset(&x, 0, sizeof x);
+      x.bad_offset = RMQ_OFFSET_NONE;
+      x.status = status[i];
+    }
+    for (uint32_t k = 0; k < na; ++k) {
+      rmq_restore_res& x = res[pl.accepted[k]];
+      if (key[k] == kScrubClean) {
+        x.records = items[pl.accepted[k]].count;
+        x.bytes = items[pl.accepted[k]].bytes;
+      } else {
+        x.bad_offset = key[k] >> 5;
+        x.bad_kind = (uint32_t)key[k] & 3u;
+      }
+    }
+  }
+  return restore_return(status);
+}
+
 int rmq_fault_corrupt_repair(rmq_engine* e, uint32_t dst, int64_t at) {
   if (!e) return RMQ_EINVAL;
   EngineLock g(e);
@@ -2500,7 +2612,7 @@ int rmq_profile_enable(rmq_engine* e, int enable) {
 }
 
 int rmq_profile_query(rmq_engine* e, int kernel, uint64_t* launches, double* total_ms) {
-  if (!e || kernel < 0 || kernel > 6) return RMQ_EINVAL;
+  if (!e || kernel < 0 || kernel > 7) return RMQ_EINVAL;
   EngineLock g(e);
   HIP_TRY(hipSetDevice(e->device));
   int rc = settle(e);

@@ -1,5 +1,5 @@
 // engine_internal.hpp — the engine object shared by the host-side translation units
-// (engine.cpp: C-ABI, append pipeline, fetch, control; replication.cpp: replica-log rounds;
+// (engine.cpp: C-ABI, append pipeline, fetch, control, scrub, repair, restore; replication.cpp: replica-log rounds;
 // repair_remote.cpp: the rounds of rmq_repair_remote).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -408,14 +408,14 @@ struct rmq_engine {
   uint32_t ctl_cap = 0;
   // profiling: pipeline launches are timed as one region (event before the first launch after
   // enable, event at the next drain) so no per-launch events sit between kernels; fetch kernels
-  // keep per-launch event pairs (prof[3], prof[4]), and so do every rmq_scrub (prof[2]), every rmq_repair (prof[5]) and every rmq_repair_remote (prof[6])
+  // keep per-launch event pairs (prof[3], prof[4]), and so do every rmq_scrub (prof[2]), every rmq_repair (prof[5]), every rmq_repair_remote (prof[6]) and every rmq_restore (prof[7])
   uint32_t profile = 0;
   uint32_t fetch_replay = 1;     // rmq_profile_enable(k >= 2): each fetch's kernels run k times
   uint64_t prof_fetch_runs = 0;
   uint64_t prof_launches = 0, prof_batches = 0;
   hipEvent_t prof_t0 = nullptr, prof_t1 = nullptr;
   bool prof_started = false, prof_ended = false;
-  std::vector<EvPair> prof[7];
+  std::vector<EvPair> prof[8];
   // rmq_scrub: the plan's scan and the result rows of the partitions of one call (grown on demand)
   uint64_t* d_scrub_tbase = nullptr;
   uint64_t* d_scrub_rows = nullptr;
@@ -447,6 +447,16 @@ struct rmq_engine {
     bool flip[kMaxWorld] = {};   // rmq_fault_corrupt_repair: the next response to q
     int64_t flip_at[kMaxWorld] = {};
   } rr;
+  // rmq_restore: device scratch grown on demand (a host buffer's runs, the table words, the checked
+  // items with their record scan and verdict keys)
+  struct Restore {
+    uint8_t* buf = nullptr;
+    uint64_t* tab = nullptr;
+    RestoreItem* items = nullptr;
+    uint64_t* rbase = nullptr;   // [items + 1]
+    uint64_t* key = nullptr;     // [items]
+    uint64_t buf_cap = 0, tab_cap = 0, items_cap = 0;
+  } rs;
   uint64_t repair_peer_bytes = 64ull << 20;  // RMQ_REPAIR_PEER_BYTES: segment bytes asked of one rank per round (a capacity)
   std::vector<hipEvent_t> ev_pool;
   // diagnostics: RMQ_STAMPS=<csv> records per-wave phase stamps of launch RMQ_STAMPS_AT (default 100)
@@ -521,6 +531,23 @@ int dalloc(T** p, size_t count) {
   // otherwise be zeroed after its first H2D copy).
   HIP_TRY(hipMemset(*p, 0, count * sizeof(T)));
   HIP_TRY(hipDeviceSynchronize());
+  return RMQ_OK;
+}
+
+// rmq_restore's device scratch: grown (never shrunk), RMQ_ENOMEM with the old buffer gone and
+// nothing else changed.
+template <typename T>
+int restore_grow(T** p, uint64_t* cap, uint64_t need) {
+  if (*cap >= need && *p) return RMQ_OK;
+  if (*p) hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  if (hipMalloc((void**)p, (size_t)need * sizeof(T)) != hipSuccess) {
+    (void)hipGetLastError();
+    *p = nullptr;
+    return RMQ_ENOMEM;
+  }
+  *cap = need;
   return RMQ_OK;
 }
 

@@ -533,6 +533,24 @@ struct RemoteInstallArgs {
   uint32_t world, pad;
 };
 
+// rmq_restore (restore.hip, FORMAT.md §11): the items that passed the host checks, in call order.
+struct RestoreItem {      // 64 bytes
+  uint64_t first_off, first_pos, count, bytes;
+  const uint8_t* run;     // device address of the run's first byte (16-byte aligned)
+  const uint64_t* tab;    // device address of its count + 1 table words
+  uint64_t commit;
+  uint32_t pidx, pad;
+};
+struct RestoreArgs {
+  DevState st;
+  StateSet sets[2];       // a restored partition gets both sets equal
+  const CrcConsts* crc;
+  const RestoreItem* items;  // [n]
+  const uint64_t* rbase;  // [n + 1] exclusive scan of the items' record counts
+  uint64_t* key;          // [n] lowest failure key (offset << 5 | kind) or kScrubClean: verify -> install
+  uint32_t n, pad;
+};
+
 // launchers (defined in the .hip files)
 // start: an event the dispatch records as the kernel starts (profiling), or null
 void launch_pipeline(const PipeArgs& a, hipStream_t s, hipEvent_t start = nullptr);
@@ -567,6 +585,9 @@ void launch_remote_request(const RemoteReqArgs& a, uint32_t wgs, hipStream_t s);
 void launch_remote_serve_check(const RemoteServeArgs& a, hipStream_t s);  // a wave per request: verdict and span bytes
 void launch_remote_serve_copy(const RemoteServeArgs& a, hipStream_t s);   // header, directory, passing spans
 void launch_remote_install(const RemoteInstallArgs& a, hipStream_t s);
+// records: rbase[n] as the host summed it; max_wgs caps both record grids
+void launch_restore_verify(const RestoreArgs& a, uint64_t records, uint32_t max_wgs, hipStream_t s);
+void launch_restore_install(const RestoreArgs& a, uint64_t records, uint32_t max_wgs, hipStream_t s);  // records, then state
 
 }  // namespace rmq
 

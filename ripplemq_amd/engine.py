@@ -71,6 +71,13 @@ REPAIR_REMOTE_RES_DTYPE = np.dtype([
     ("segments_unrepaired", "<u8"), ("bad_offset", "<u8"), ("bad_replica", "<u4"), ("bad_kind", "<u4"),
     ("replicas", "<u4"), ("status", "<i4"),
 ])
+RESTORE_ITEM_DTYPE = np.dtype([
+    ("pidx", "<u4"), ("flags", "<u4"), ("first_offset", "<u8"), ("first_pos", "<u8"), ("count", "<u8"),
+    ("bytes", "<u8"), ("buf_pos", "<u8"), ("table_start", "<u8"), ("commit", "<u8"),
+])
+RESTORE_RES_DTYPE = np.dtype([
+    ("records", "<u8"), ("bytes", "<u8"), ("bad_offset", "<u8"), ("bad_kind", "<u4"), ("status", "<i4"),
+])
 STATE_FIELDS = ("log_end_offset", "log_end_pos", "log_start_offset", "log_start_pos", "commit",
                 "high_watermark", "term", "term_start", "leader_commit", "last_log_term", "voted_term",
                 "voted_for", "led", "heard_round")
@@ -600,6 +607,30 @@ class Engine:
             raise EngineError(rc, "rmq_repair_remote")
         self.last_repair_rc = rc
         self.last_repair_served = (int(served[0]), int(served[1]))
+        return out
+
+    def restore(self, items, buf, rec_pos, dry_run: bool = False, mem: int = A.RMQ_MEM_HOST,
+                buf_bytes: int | None = None) -> np.ndarray:
+        """rmq_restore: restart pristine partitions from record images (FORMAT.md §11). items: a
+        RESTORE_ITEM_DTYPE array; buf: the runs, a uint8 array (mem = RMQ_MEM_HOST) or a device
+        address with buf_bytes (RMQ_MEM_DEVICE); rec_pos: the uint64 position table. Returns a
+        RESTORE_RES_DTYPE row per item. A refused row raises nothing (its status says why);
+        self.last_restore_rc keeps the call's return value. A call-level failure (a transport is
+        attached, no memory, a device error) raises. dry_run verifies and writes nothing."""
+        items = np.atleast_1d(np.ascontiguousarray(items, RESTORE_ITEM_DTYPE))
+        rec_pos = np.ascontiguousarray(rec_pos, np.uint64)
+        if mem == A.RMQ_MEM_HOST:
+            buf = np.ascontiguousarray(buf, np.uint8)
+            bp, nb = (_ptr(buf) if buf.size else None), buf.size
+        else:
+            bp, nb = buf, int(buf_bytes)
+        out = np.zeros(len(items), RESTORE_RES_DTYPE)
+        rc = self.lib.rmq_restore(self.h, len(items), _ptr(items) if len(items) else None, mem, bp, nb,
+                                  _ptr(rec_pos) if rec_pos.size else None, rec_pos.size,
+                                  A.RMQ_RESTORE_DRY_RUN if dry_run else 0, _ptr(out) if len(items) else None)
+        if rc and not (len(out) and (out["status"] == rc).any()):
+            raise EngineError(rc, "rmq_restore")
+        self.last_restore_rc = rc
         return out
 
     def fault_corrupt_repair(self, dst: int, at: int) -> None:

@@ -592,3 +592,99 @@ def replay(directory: str, engine, partitions, *, batch_records: int = 65536) ->
                 raise EngineError(rc, f"replay of partition {p}: consumer offsets")
             rows += 1
     return {"records": total, "partitions": len(recs), "terms": terms, "offset_rows": rows}
+
+
+def restore(directory: str, engine, partitions, *, base_pos=None, max_call_bytes: int = 256 << 20) -> dict:
+    """Load a fresh engine's logs from segment files on the device (rmq_restore, FORMAT.md §11): for
+    every partition the longest suffix of whole durable records whose bytes fit its ring goes to the
+    engine as it lies in the files, with the record positions the files' walk gave, in calls of at
+    most ``max_call_bytes`` of runs (a larger partition goes alone). The engine verifies every record
+    before it writes one; a refused partition raises. Unlike ``replay`` the files need not start at
+    offset 0, followed partitions load like led ones, and nothing below the retained window is read.
+    A log's positions must equal its peers' (FORMAT.md §9): files that start at offset 0 give them;
+    otherwise ``base_pos[p]`` is the logical position of the files' first record, and a partition
+    without one raises RMQ_EINVAL. Every durable record is committed, so the restored commit is the
+    durable end. Then consumer-offset rows, terms, votes and (only where the replica led) leadership
+    come back exactly as in ``replay``. Returns the counts ``replay`` returns."""
+    from .engine import RESTORE_ITEM_DTYPE
+
+    ends = load_ends(directory)
+    files = {int(p): _PartitionFiles(directory, int(p), 1 << 62, ends.get(int(p), 0)) for p in partitions}
+    seg = engine.states()["segment_bytes"]
+    plan = []  # (partition, files, first record of the suffix, its item fields)
+    for p, f in files.items():
+        pos = f.pos
+        if len(pos) < 2:
+            continue
+        total = int(pos[-1])
+        k = int(np.searchsorted(pos, total - int(seg[p]), side="left"))
+        if f.base == 0:
+            origin = 0
+        elif base_pos is not None and (base_pos.get(p) if hasattr(base_pos, "get") else base_pos[p]) is not None:
+            origin = int(base_pos[p])
+        else:
+            raise EngineError(A.RMQ_EINVAL, f"restore of partition {p}: files start at offset {f.base} and no "
+                                            f"base position is given (positions must equal the peers')")
+        plan.append((p, f, k, total - int(pos[k]), origin))
+    records = 0
+    g = 0
+    while g < len(plan):
+        h, nbytes = g, 0
+        while h < len(plan) and (h == g or nbytes + plan[h][3] <= max_call_bytes):
+            nbytes += plan[h][3]
+            h += 1
+        items = np.zeros(h - g, RESTORE_ITEM_DTYPE)
+        buf = np.empty(nbytes, np.uint8)
+        tabs, at, words = [], 0, 0
+        for i, (p, f, k, nb, origin) in enumerate(plan[g:h]):
+            pos = f.pos
+            rel = (pos[k:] - pos[k]).astype(np.uint64)
+            buf[at:at + nb] = np.frombuffer(f.read_bytes(int(pos[k]), int(pos[-1])), np.uint8)
+            items[i] = (p, 0, f.base + k, origin + int(pos[k]), len(rel) - 1, nb, at, words, f.end)
+            tabs.append(rel)
+            at += nb
+            words += len(rel)
+        rows = engine.restore(items, buf, np.concatenate(tabs))
+        bad = np.flatnonzero(rows["status"] != A.RMQ_OK)
+        if len(bad):
+            p, st = int(items["pidx"][bad[0]]), int(rows["status"][bad[0]])
+            what = (f" (record {int(rows['bad_offset'][bad[0]])} fails its checks)" if st == A.RMQ_ECORRUPT else "")
+            raise EngineError(st, f"restore of partition {p}{what}")
+        records += int(rows["records"].sum())
+        g = h
+    # terms, votes and consumer rows as replay restores them, with the states read in bulk and the
+    # rows committed in calls of whole partitions (a row is one version step per call either way)
+    terms = rows_n = 0
+    sts = engine.states()
+    cp, cc, co = [], [], []
+
+    def commit_rows():
+        if cp:
+            rc, _ = engine.commit_consumer_offset(np.concatenate(cp), np.concatenate(cc), np.concatenate(co))
+            if rc:
+                raise EngineError(rc, f"restore of partitions {int(cp[0][0])}..{int(cp[-1][0])}: consumer offsets")
+            cp.clear(), cc.clear(), co.clear()
+
+    for p, f in files.items():
+        meta = f.load_meta()
+        term = int(meta.get("term", 0))
+        vt, vf = int(meta.get("voted_term", 0)), int(meta.get("voted_for", A.RMQ_NO_VOTE))
+        led = int(meta.get("led", 1))
+        voted = int(sts["voted_term"][p])
+        if led and term > int(sts["term"][p]):
+            engine.become_leader(p, term)
+            voted = engine.state(p)["voted_term"]  # (a leader votes for itself)
+            terms += 1
+        if vt > voted:
+            engine.set_vote(p, vt, vf)
+            terms += 0 if led else 1
+        raw = f.load_offsets_bytes()
+        if raw:
+            offs = np.frombuffer(raw, np.uint64).copy()
+            n = min(len(offs), engine.cfg.max_consumers)
+            cp.append(np.full(n, p, np.uint32)), cc.append(np.arange(n, dtype=np.uint32)), co.append(offs[:n])
+            rows_n += 1
+            if len(cp) * engine.cfg.max_consumers >= 1 << 15:
+                commit_rows()
+    commit_rows()
+    return {"records": records, "partitions": len(plan), "terms": terms, "offset_rows": rows_n}
