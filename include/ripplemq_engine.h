@@ -488,6 +488,51 @@ typedef struct rmq_repair_res {
    repairs only the slots it holds. */
 int rmq_repair(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags, rmq_repair_res* res);
 
+/* ---- index rebuild (added after ABI 11 without a bump, as rmq_repair was: one struct, two flags
+   and two functions, nothing existing moves) ---- */
+#define RMQ_REINDEX_DRY_RUN 1u  /* walk and count, write nothing */
+#define RMQ_REINDEX_ALL     2u  /* trust no stored entry: one walk per partition from the log start */
+typedef struct rmq_reindex_res {
+  uint64_t entries_live;       /* live entries of the partition, hi - lo + 1 (0 if none) */
+  uint64_t entries_rewritten;  /* live entries whose stored value the call changed (dry run: would change) */
+  uint64_t gaps_unresolved;    /* gaps whose walk did not complete: their entries are left as they were */
+  uint64_t bad_offset;         /* what remains AFTER the call, as rmq_scrub_res reports it */
+  uint32_t bad_replica;
+  uint32_t bad_kind;
+  uint32_t replicas;
+  int32_t status;              /* RMQ_OK, or RMQ_ECORRUPT if something remains */
+} rmq_reindex_res;             /* 48 bytes */
+/* Scrub, then rebuild damaged sparse-index entries from the log, then scrub again (FORMAT.md §10
+   "Index rebuild"). The index is one per partition, so a damaged entry fails its two adjoining
+   segments on every local slot alike and neither repair has a donor for it; the records that define
+   it are intact on the slots. The first pass is rmq_repair's. A segment that passes on no local slot
+   is bad, a maximal run of bad segments is a gap, and one walk per gap starts at the gap's start
+   boundary (the log start, or the stored entry that ends the passing segment before it) and
+   accepts each record that passes the scrub's checks on some local slot, lowest slot first, so a
+   record damaged on one slot does not stop it. Entry m is {offset, pos} of the first record start
+   at logical position >= m * interval, the log end counting as one. A gap is resolved when its
+   walk reaches the stored entry that ends it with exactly that value (the log end, for a gap that
+   ends the log); only then are its live entries that differ from the rebuilt ones written, and the
+   partition's position-cache rows emptied. An unresolved gap (a record that passes on no slot or
+   runs past the span, another value at the gap's end, a partition state no log can have) is counted
+   in gaps_unresolved and nothing of it is written. With RMQ_REINDEX_ALL there is one walk per
+   partition with a local slot, from the log start to the log end, trusting no stored entry: the
+   only mode that corrects an entry the scrub passes because it names a true record start that is
+   not the first one at or after its multiple; it is serial per partition. Ring bytes, partition
+   state, consumer offsets and index slots outside the live range are never written. The range is
+   then audited again: bad_offset, bad_replica, bad_kind, replicas and status are the scrub's row
+   of the state the call leaves. With RMQ_REINDEX_DRY_RUN the counters are those the real call
+   would return, the other fields describe the present state and no byte changes. Call order for a
+   damaged replica: rmq_reindex, then rmq_repair, then rmq_repair_remote. res (host, [n], nullable).
+   Returns RMQ_OK if every partition of the range is clean afterwards, RMQ_ECORRUPT if any is not,
+   RMQ_ENOPART if the range leaves [0, P), RMQ_EINVAL for an unknown flag bit. Drains first: with a
+   transport attached the call is collective, and each rank rebuilds its own index. */
+int rmq_reindex(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags, rmq_reindex_res* res);
+/* Fault injection (tests): XORs xor_mask into word `word` (0 offset, 1 pos) of index slot
+   m mod icap of pidx, as a memory corruption would. RMQ_ENOPART for a bad pidx, RMQ_EINVAL for
+   word > 1 or a zero mask. Drains first (collective with a transport, like rmq_sync). */
+int rmq_fault_flip_index(rmq_engine* e, uint32_t pidx, uint64_t m, uint32_t word, uint64_t xor_mask);
+
 /* ---- remote repair (added after ABI 11 without a bump, as rmq_repair was: one struct and two
    functions, nothing existing moves) ---- */
 typedef struct rmq_repair_remote_res {
@@ -626,6 +671,7 @@ int rmq_host_unregister(rmq_engine* e, void* p);
    last, launches = calls. 6: rmq_repair_remote, from before its first plan to after its last kernel
    (the exchanges and the host's waits between them included), launches = calls. 7: rmq_restore, an
    event before its first kernel to one after its last (the staging copies before them outside),
+   launches = calls. 8: rmq_reindex, an event before its first plan to one after its last kernel,
    launches = calls. */
 int rmq_profile_enable(rmq_engine* e, int enable);
 int rmq_profile_query(rmq_engine* e, int kernel, uint64_t* launches, double* total_ms);

@@ -30,6 +30,8 @@ RMQ_SCAN_CHECK = 1
 RMQ_SCRUB_BAD_CRC = 1
 RMQ_SCRUB_BAD_CHAIN = 2
 RMQ_REPAIR_DRY_RUN = 1
+RMQ_REINDEX_DRY_RUN = 1
+RMQ_REINDEX_ALL = 2
 RMQ_RESTORE_DRY_RUN = 1
 
 RMQ_OK = 0
@@ -123,6 +125,13 @@ class RmqRepairRes(C.Structure):
     ]
 
 
+class RmqReindexRes(C.Structure):
+    _fields_ = [
+        ("entries_live", u64), ("entries_rewritten", u64), ("gaps_unresolved", u64),
+        ("bad_offset", u64), ("bad_replica", u32), ("bad_kind", u32), ("replicas", u32), ("status", i32),
+    ]
+
+
 class RmqRepairRemoteRes(C.Structure):
     _fields_ = [
         ("segments_repaired", u64), ("bytes_repaired", u64), ("segments_fetched", u64), ("bytes_fetched", u64),
@@ -208,6 +217,8 @@ _SIGS = {
     "rmq_scrub": (C.c_int, [vp, u32, u32, vp]),
     "rmq_fault_flip_ring": (C.c_int, [vp, u32, u32, u64, u32]),
     "rmq_repair": (C.c_int, [vp, u32, u32, u32, vp]),
+    "rmq_reindex": (C.c_int, [vp, u32, u32, u32, vp]),
+    "rmq_fault_flip_index": (C.c_int, [vp, u32, u64, u32, u64]),
     "rmq_repair_remote": (C.c_int, [vp, u32, u32, u32, vp, C.POINTER(u64)]),
     "rmq_fault_corrupt_repair": (C.c_int, [vp, u32, C.c_int64]),
     "rmq_restore": (C.c_int, [vp, u32, vp, u32, vp, u64, vp, u64, u32, vp]),

@@ -596,7 +596,8 @@ void free_engine(rmq_engine* e) {
                              s.local_mask, s.index, s.logs, s.ring, s.cons, s.pcache, s.rcur, s.cdirty, s.lcommit, s.csnap, s.cver, s.cq,
                              s.lterm, s.mterm, s.heard, e->d_crc,
                              e->d_stats, e->d_ctl32, e->d_ctl64, e->d_stamps, e->d_rlate, e->d_scrub_tbase, e->d_scrub_rows,
-                             e->d_repair_verdict, e->d_repair_counts, e->rs.buf, e->rs.tab, e->rs.items, e->rs.rbase,
+                             e->d_repair_verdict, e->d_repair_counts, e->d_reindex_gaps, e->d_reindex_scratch,
+                             e->d_reindex_counts, e->rs.buf, e->rs.tab, e->rs.items, e->rs.rbase,
                              e->rs.key};
   repair_remote_free(e);
   if (e->state_stage) hipHostFree(e->state_stage);
@@ -2307,6 +2308,114 @@ int rmq_repair(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags, rmq_re
   return corrupt ? RMQ_ECORRUPT : RMQ_OK;
 }
 
+// The repair's first pass, then the gaps, the walks and the install of reindex.hip on the same plan,
+// then (if an entry changed) the audit again.
+int rmq_reindex(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags, rmq_reindex_res* res) {
+  if (!e || (flags & ~(RMQ_REINDEX_DRY_RUN | RMQ_REINDEX_ALL))) return RMQ_EINVAL;
+  EngineLock g(e);
+  const uint32_t P = e->cfg.num_partitions, RF = e->cfg.replication_factor;
+  if (first > P || n > P - first) return RMQ_ENOPART;
+  if (!n) return RMQ_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  int rc = drain(e);
+  if (rc) return rc;
+  rc = scrub_buffers(e, n);
+  if (rc) return rc;
+  // the repair's task bound: a verdict per task, and a gap and a rebuilt entry per task at the most
+  // (a partition with a local slot has at least as many tasks as live entries plus one)
+  uint64_t tasks = 0;
+  for (uint32_t p = first; p < first + n; ++p)
+    tasks += RF * (((1ull << (e->ring[p] & 63ull)) >> e->st.interval_log2) + 2ull);
+  if (e->repair_verdict_cap < tasks) {
+    if (e->d_repair_verdict) hipFree(e->d_repair_verdict);
+    e->d_repair_verdict = nullptr;
+    e->repair_verdict_cap = 0;
+    rc = dalloc(&e->d_repair_verdict, (size_t)tasks);
+    if (rc) return rc;
+    e->repair_verdict_cap = tasks;
+  }
+  if (e->reindex_cap < tasks) {
+    if (e->d_reindex_gaps) hipFree(e->d_reindex_gaps);
+    if (e->d_reindex_scratch) hipFree(e->d_reindex_scratch);
+    e->d_reindex_gaps = e->d_reindex_scratch = nullptr;
+    e->reindex_cap = 0;
+    rc = dalloc(&e->d_reindex_gaps, (size_t)tasks * 2);
+    if (!rc) rc = dalloc(&e->d_reindex_scratch, (size_t)tasks * 2);
+    if (rc) return rc;
+    e->reindex_cap = tasks;
+  }
+  if (e->reindex_counts_cap < n) {
+    if (e->d_reindex_counts) hipFree(e->d_reindex_counts);
+    e->d_reindex_counts = nullptr;
+    e->reindex_counts_cap = 0;
+    rc = dalloc(&e->d_reindex_counts, (size_t)n * 3 + 1);
+    if (rc) return rc;
+    e->reindex_counts_cap = n;
+  }
+  ReindexArgs a{};
+  a.s.st = e->st;
+  a.s.crc = e->d_crc;
+  a.s.tbase = e->d_scrub_tbase;
+  a.s.rows = e->d_scrub_rows;
+  a.s.first = first;
+  a.s.n = n;
+  a.verdict = e->d_repair_verdict;
+  a.gaps = e->d_reindex_gaps;
+  a.scratch = e->d_reindex_scratch;
+  a.counts = e->d_reindex_counts;
+  a.ngaps = reinterpret_cast<uint32_t*>(e->d_reindex_counts + (size_t)n * 3);
+  a.cap = tasks;  // (>= n: every partition of the range adds at least 2 RF)
+  a.all = (flags & RMQ_REINDEX_ALL) ? 1u : 0u;
+  a.write = (flags & RMQ_REINDEX_DRY_RUN) ? 0u : 1u;
+  RepairArgs ra{};
+  ra.s = a.s;
+  ra.verdict = e->d_repair_verdict;
+  hipEvent_t r0 = nullptr, r1 = nullptr;
+  if (e->profile) {  // kernel 8: an event before the first plan to one after the last kernel of the call
+    r0 = pool_event(e);
+    r1 = pool_event(e);
+    e->prof[8].push_back({r0, r1});
+    HIP_TRY(hipEventRecord(r0, e->main_s));
+  }
+  std::vector<uint64_t> rows((size_t)n * 4), counts((size_t)n * 3, 0);
+  HIP_TRY(hipMemsetAsync(e->d_reindex_counts, 0, (counts.size() + 1) * 8, e->main_s));
+  launch_repair_scan(ra, audit_wgs(e), e->main_s);
+  launch_reindex(a, audit_wgs(e), e->main_s);
+  HIP_TRY(hipGetLastError());
+  if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));  // (recorded again below if the audit follows)
+  rc = stream_wait(e->main_s);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpy(rows.data(), e->d_scrub_rows, rows.size() * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(counts.data(), e->d_reindex_counts, counts.size() * 8, hipMemcpyDeviceToHost));
+  bool wrote = false;
+  for (uint32_t i = 0; i < n && !wrote; ++i) wrote = a.write && counts[3ull * i + 1] != 0;
+  if (wrote) {
+    launch_scrub(a.s, audit_wgs(e), e->main_s);
+    HIP_TRY(hipGetLastError());
+    if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
+    rc = stream_wait(e->main_s);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(rows.data(), e->d_scrub_rows, rows.size() * 8, hipMemcpyDeviceToHost));
+  }
+  bool corrupt = false;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint64_t key = rows[4ull * i];
+    corrupt = corrupt || key != kScrubClean;
+    if (!res) continue;
+    rmq_reindex_res& x = res[i];
+    std::memset(&x, 0, sizeof x);
+    x.entries_live = counts[3ull * i];
+    x.entries_rewritten = counts[3ull * i + 1];
+    x.gaps_unresolved = counts[3ull * i + 2];
+    x.replicas = (uint32_t)rows[4ull * i + 3];
+    x.bad_offset = key == kScrubClean ? RMQ_OFFSET_NONE : key >> 5;
+    x.bad_replica = key == kScrubClean ? 0u : (uint32_t)(key >> 2) & 7u;
+    x.bad_kind = key == kScrubClean ? 0u : (uint32_t)key & 3u;
+    x.status = key == kScrubClean ? RMQ_OK : RMQ_ECORRUPT;
+  }
+  return corrupt ? RMQ_ECORRUPT : RMQ_OK;
+}
+
 // rmq_repair's first pass and local copy, then the rounds over the transport (repair_remote.cpp),
 // then the audit again. Without a transport this is rmq_repair step by step.
 int rmq_repair_remote(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags, rmq_repair_remote_res* res,
@@ -2555,6 +2664,24 @@ int rmq_fault_flip_ring(rmq_engine* e, uint32_t replica, uint32_t p, uint64_t ri
   return RMQ_OK;
 }
 
+int rmq_fault_flip_index(rmq_engine* e, uint32_t pidx, uint64_t m, uint32_t word, uint64_t xor_mask) {
+  if (!e) return RMQ_EINVAL;
+  EngineLock g(e);
+  if (pidx >= e->cfg.num_partitions) return RMQ_ENOPART;
+  if (word > 1u || !xor_mask) return RMQ_EINVAL;
+  const RingRef rg = ring_ref(e->ring[pidx], e->st.interval_log2, e->st.icap_mul);
+  HIP_TRY(hipSetDevice(e->device));
+  int rc = drain(e);
+  if (rc) return rc;
+  // one word of the partition's own index ring
+  uint64_t* at = e->st.index + (rg.ibase + m % rg.icap) * 2 + word;
+  uint64_t w = 0;
+  HIP_TRY(hipMemcpy(&w, at, 8, hipMemcpyDeviceToHost));
+  w ^= xor_mask;
+  HIP_TRY(hipMemcpy(at, &w, 8, hipMemcpyHostToDevice));
+  return RMQ_OK;
+}
+
 int rmq_device_alloc(rmq_engine* e, uint64_t bytes, void** out) {
   if (!e || !out) return RMQ_EINVAL;
   EngineLock g(e);
@@ -2612,7 +2739,7 @@ int rmq_profile_enable(rmq_engine* e, int enable) {
 }
 
 int rmq_profile_query(rmq_engine* e, int kernel, uint64_t* launches, double* total_ms) {
-  if (!e || kernel < 0 || kernel > 7) return RMQ_EINVAL;
+  if (!e || kernel < 0 || kernel > 8) return RMQ_EINVAL;
   EngineLock g(e);
   HIP_TRY(hipSetDevice(e->device));
   int rc = settle(e);

@@ -408,14 +408,14 @@ struct rmq_engine {
   uint32_t ctl_cap = 0;
   // profiling: pipeline launches are timed as one region (event before the first launch after
   // enable, event at the next drain) so no per-launch events sit between kernels; fetch kernels
-  // keep per-launch event pairs (prof[3], prof[4]), and so do every rmq_scrub (prof[2]), every rmq_repair (prof[5]), every rmq_repair_remote (prof[6]) and every rmq_restore (prof[7])
+  // keep per-launch event pairs (prof[3], prof[4]), and so do every rmq_scrub (prof[2]), every rmq_repair (prof[5]), every rmq_repair_remote (prof[6]), every rmq_restore (prof[7]) and every rmq_reindex (prof[8])
   uint32_t profile = 0;
   uint32_t fetch_replay = 1;     // rmq_profile_enable(k >= 2): each fetch's kernels run k times
   uint64_t prof_fetch_runs = 0;
   uint64_t prof_launches = 0, prof_batches = 0;
   hipEvent_t prof_t0 = nullptr, prof_t1 = nullptr;
   bool prof_started = false, prof_ended = false;
-  std::vector<EvPair> prof[8];
+  std::vector<EvPair> prof[9];
   // rmq_scrub: the plan's scan and the result rows of the partitions of one call (grown on demand)
   uint64_t* d_scrub_tbase = nullptr;
   uint64_t* d_scrub_rows = nullptr;
@@ -425,6 +425,13 @@ struct rmq_engine {
   uint64_t repair_verdict_cap = 0;
   uint64_t* d_repair_counts = nullptr;
   uint32_t repair_counts_cap = 0;
+  // rmq_reindex: the gap list and the rebuilt entries (a pair of words per task of the bound), the
+  // gap counter and the counters of the range's partitions
+  uint64_t* d_reindex_gaps = nullptr;
+  uint64_t* d_reindex_scratch = nullptr;
+  uint64_t reindex_cap = 0;
+  uint64_t* d_reindex_counts = nullptr;  // [n][3], then the gap counter's word
+  uint32_t reindex_counts_cap = 0;
   // rmq_repair_remote (repair_remote.cpp): device buffers grown on demand (a capacity next to each),
   // fixed control words with their page-locked mirror, the per-destination budget and the fault hook
   struct RemoteRepair {

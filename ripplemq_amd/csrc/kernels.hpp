@@ -474,6 +474,21 @@ struct RepairArgs {
   uint32_t write;     // 0: count only (RMQ_REPAIR_DRY_RUN)
 };
 
+// rmq_reindex (reindex.hip, FORMAT.md §10 "Index rebuild"): the first pass of the repair, the gap
+// list, the rebuilt entries and the counters of the partitions of the range.
+struct ReindexArgs {
+  ScrubArgs s;
+  const uint8_t* verdict;  // [tasks] the first pass's verdicts
+  uint64_t* gaps;     // [cap][2] {partition of the range << 48 | first bad segment, resolved << 63 | end of
+                      //   the rebuilt entries}: gaps kernel -> walk -> install (ALL: gap g is partition g)
+  uint32_t* ngaps;    // [1] gaps appended (zero at the start)
+  uint64_t* scratch;  // [cap][2] rebuilt entry m of partition i at tbase[i] + (m - lo)
+  uint64_t* counts;   // [n][3] {live entries, entries rewritten, gaps unresolved} (zero at the start)
+  uint64_t cap;       // the host's task bound: slots of gaps and of scratch
+  uint32_t all;       // RMQ_REINDEX_ALL
+  uint32_t write;     // 0: count only (RMQ_REINDEX_DRY_RUN)
+};
+
 // rmq_repair_remote (repair_remote.hip, FORMAT.md §10 "Remote repair"): the wire sizes, and the
 // arguments of the request, serve and install kernels of one round.
 constexpr uint32_t kRemoteMagic = 0x31525152u;  // "RQR1": request list and response headers
@@ -581,6 +596,7 @@ void launch_scrub(const ScrubArgs& a, uint32_t verify_wgs, hipStream_t s);  // p
 void launch_scrub_plan(const ScrubArgs& a, hipStream_t s);
 void launch_repair_scan(const RepairArgs& a, uint32_t wgs, hipStream_t s);  // plan, then verify with verdicts
 void launch_repair_copy(const RepairArgs& a, uint32_t wgs, hipStream_t s);
+void launch_reindex(const ReindexArgs& a, uint32_t wgs, hipStream_t s);  // after launch_repair_scan: gaps, walk, install
 void launch_remote_request(const RemoteReqArgs& a, uint32_t wgs, hipStream_t s);
 void launch_remote_serve_check(const RemoteServeArgs& a, hipStream_t s);  // a wave per request: verdict and span bytes
 void launch_remote_serve_copy(const RemoteServeArgs& a, hipStream_t s);   // header, directory, passing spans

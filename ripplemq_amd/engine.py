@@ -66,6 +66,10 @@ REPAIR_RES_DTYPE = np.dtype([
     ("segments_repaired", "<u8"), ("bytes_repaired", "<u8"), ("segments_unrepaired", "<u8"),
     ("bad_offset", "<u8"), ("bad_replica", "<u4"), ("bad_kind", "<u4"), ("replicas", "<u4"), ("status", "<i4"),
 ])
+REINDEX_RES_DTYPE = np.dtype([
+    ("entries_live", "<u8"), ("entries_rewritten", "<u8"), ("gaps_unresolved", "<u8"),
+    ("bad_offset", "<u8"), ("bad_replica", "<u4"), ("bad_kind", "<u4"), ("replicas", "<u4"), ("status", "<i4"),
+])
 REPAIR_REMOTE_RES_DTYPE = np.dtype([
     ("segments_repaired", "<u8"), ("bytes_repaired", "<u8"), ("segments_fetched", "<u8"), ("bytes_fetched", "<u8"),
     ("segments_unrepaired", "<u8"), ("bad_offset", "<u8"), ("bad_replica", "<u4"), ("bad_kind", "<u4"),
@@ -591,6 +595,24 @@ class Engine:
         self.last_repair_rc = rc
         return out
 
+    def reindex(self, first: int = 0, n: int | None = None, dry_run: bool = False, all: bool = False) -> np.ndarray:
+        """rmq_reindex: scrub partitions [first, first + n), rebuild the sparse-index entries of every
+        gap (a maximal run of segments that pass on no local slot) by walking the log's records, and
+        scrub again (FORMAT.md §10, "Index rebuild"): a structured array of rmq_reindex_res, one row
+        per partition. all trusts no stored entry (one walk per partition, from the log start);
+        dry_run counts what would be rewritten and writes nothing. What remains raises nothing (the
+        rows say where it is); self.last_reindex_rc keeps the call's return value, RMQ_OK or
+        RMQ_ECORRUPT. Call it before repair() and repair_remote(). Drains first (collective with a
+        transport)."""
+        n = self.cfg.num_partitions - first if n is None else n
+        flags = (A.RMQ_REINDEX_DRY_RUN if dry_run else 0) | (A.RMQ_REINDEX_ALL if all else 0)
+        out = np.zeros(max(n, 0), REINDEX_RES_DTYPE)
+        rc = self.lib.rmq_reindex(self.h, first, n, flags, _ptr(out) if n else None)
+        if rc not in (A.RMQ_OK, A.RMQ_ECORRUPT):
+            raise EngineError(rc, "rmq_reindex")
+        self.last_reindex_rc = rc
+        return out
+
     def repair_remote(self, first: int = 0, n: int | None = None, dry_run: bool = False) -> np.ndarray:
         """rmq_repair_remote: repair(), then the pairs it had to leave are fetched from the ranks that
         hold the partition's other replica slots and installed once they verify here (FORMAT.md §10,
@@ -642,6 +664,11 @@ class Engine:
         """Tests: XOR one byte of a local replica ring (rmq_fault_flip_ring), addressed as
         read_segment addresses it."""
         _check(self.lib.rmq_fault_flip_ring(self.h, replica, pidx, ring_off, xor_mask), "rmq_fault_flip_ring")
+
+    def fault_flip_index(self, pidx: int, m: int, word: int, xor_mask: int) -> None:
+        """Tests: XOR xor_mask into word `word` (0 offset, 1 pos) of index entry m of pidx
+        (rmq_fault_flip_index)."""
+        _check(self.lib.rmq_fault_flip_index(self.h, pidx, m, word, xor_mask), "rmq_fault_flip_index")
 
     def consumer_offsets(self, pidx: int) -> np.ndarray:
         out = np.empty(self.cfg.max_consumers, np.uint64)
