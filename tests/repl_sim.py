@@ -32,14 +32,34 @@ def rank_batches(spec: StreamSpec, rank: int, rounds: int, group: int):
     return [make_batch(spec, 1000 * rank + k) for k in range(rounds * group)]
 
 
-def exchange_round(oras, keep_regions: bool = False, corrupt=None, skip=None, drop=(), lost=()):
+def flip_at(region: np.ndarray, at) -> int:
+    """The byte of `region` that rmq_fault_corrupt(at) flips: at >= 0 counts from the region's start,
+    at < 0 from the end of its data section; a callable is given the clean region and returns at."""
+    if callable(at):
+        at = at(region)
+    at = int(at)
+    if at < 0:
+        at += int(region[32:40].view(np.uint64)[0])  # rows_off: end of the data section
+    return at
+
+
+def exchange_round(oras, keep_regions: bool = False, corrupt=None, skip=None, drop=(), lost=(), trace=None):
     """Regions of every leader to every follower, ingested there; acks back to the leaders (FORMAT.md
     §9 v3: a refused ack leaves a catch-up request for the next round's plan).
     corrupt=(src, dst, byte): flip one byte of that region (byte < 0: from the end of its data
-    section, i.e. a payload byte of its last record); skip=(src, dst): drop that region and its
+    section, i.e. a payload byte of its last record), or a list of such triples (at most one per
+    pair), where byte may be a callable on the clean region; skip=(src, dst): drop that region and its
     acks; drop: leaders whose round sends no region (rmq_fault_drop_rounds: their followers miss
     the round and refuse every entry of it); lost: (src, dst) pairs whose region is lost on the way
-    (rmq_fault_isolate: dst misses src's round)."""
+    (rmq_fault_isolate: dst misses src's round). trace: a dict that receives "flips", the
+    [(src, dst, byte from the region's start)] applied, and "acks", {(src, dst): the acks}."""
+    flips = {}
+    if corrupt:
+        for s, d, at in ([corrupt] if not isinstance(corrupt[0], (tuple, list)) else corrupt):
+            assert (s, d) not in flips, "one flip per region and round (rmq_fault_corrupt keeps one)"
+            flips[(s, d)] = at
+    if trace is not None:
+        trace["flips"], trace["acks"] = [], {}
     W = len(oras)
     rnd = [o.round_no() for o in oras]
     regions = [[oras[s].round_region(d) if d != s else None for d in range(W)] for s in range(W)]
@@ -56,13 +76,15 @@ def exchange_round(oras, keep_regions: bool = False, corrupt=None, skip=None, dr
             if regions[s][d].size == 0 and s not in drop and (s, d) not in lost:
                 continue
             reg = regions[s][d]
-            if corrupt and (s, d) == tuple(corrupt[:2]):
+            if (s, d) in flips:
+                at = flip_at(reg, flips[(s, d)])
                 reg = reg.copy()
-                at = corrupt[2]
-                if at < 0:
-                    at += int(reg[32:40].view(np.uint64)[0])  # rows_off: end of the data section
                 reg[at] ^= 0x5A
+                if trace is not None:
+                    trace["flips"].append((s, d, at))
             acks = oras[d].ingest(s, reg)
+            if trace is not None:
+                trace["acks"][(s, d)] = acks.copy()
             oras[s].apply_acks(d, acks, rnd[s])
     return regions if keep_regions else None
 
