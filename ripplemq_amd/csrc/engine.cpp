@@ -11,10 +11,10 @@
 // append path: launch k reports launch k-1 complete through a host-visible word, and the tail is
 // read with hipStreamQuery. Control-plane calls (leadership, replicas, acks, consumer offsets,
 // fetch) flush and drain first and run synchronously: they are rare next to the append stream.
+// The audit calls (scrub, repair, reindex, remote repair, restore) are in audit.cpp.
 #include <chrono>
 
 #include "engine_internal.hpp"
-#include "restore_check.hpp"
 
 using namespace rmq;
 
@@ -118,17 +118,6 @@ int check_err(rmq_engine* e) {
   const hipError_t q = hipStreamQuery(e->main_s);
   return q == hipSuccess || q == hipErrorNotReady ? RMQ_OK : hip_fail(q);
 }
-
-int fetch_flush(rmq_engine* e);
-// The engine lock of every call: held-back asynchronous fetches go to the pipeline stream first, so
-// whatever the call issues is ordered after them (their contract); a launch error stays sticky on the
-// stream and surfaces at the next check.
-struct EngineLock {
-  std::lock_guard<std::mutex> g;
-  explicit EngineLock(rmq_engine* e) : g(e->mu) {
-    if (!e->fpend.empty() && hipSetDevice(e->device) == hipSuccess) (void)fetch_flush(e);
-  }
-};
 
 // Wait for everything issued on stream s. A blocking hipStreamSynchronize returns ~10 us after the
 // last kernel ends (interrupt wake-up); a sync sits on the producer's path (rmq_sync, a poll that
@@ -595,10 +584,9 @@ void free_engine(rmq_engine* e) {
   std::vector<void*> bufs = {s.start_off, s.start_pos, s.commit, s.hw, s.term_start, s.term, s.match, s.is_leader,
                              s.local_mask, s.index, s.logs, s.ring, s.cons, s.pcache, s.rcur, s.cdirty, s.lcommit, s.csnap, s.cver, s.cq,
                              s.lterm, s.mterm, s.heard, e->d_crc,
-                             e->d_stats, e->d_ctl32, e->d_ctl64, e->d_stamps, e->d_rlate, e->d_scrub_tbase, e->d_scrub_rows,
-                             e->d_repair_verdict, e->d_repair_counts, e->d_reindex_gaps, e->d_reindex_scratch,
-                             e->d_reindex_counts, e->rs.buf, e->rs.tab, e->rs.items, e->rs.rbase,
+                             e->d_stats, e->d_ctl32, e->d_ctl64, e->d_stamps, e->d_rlate, e->rs.buf, e->rs.tab, e->rs.items, e->rs.rbase,
                              e->rs.key};
+  audit_free(e);
   repair_remote_free(e);
   if (e->state_stage) hipHostFree(e->state_stage);
   for (rmq_engine::FetchSlot& f : e->fslot) {
@@ -1731,13 +1719,6 @@ int fetch_slot_step(rmq_engine* e, rmq_engine::FetchSlot& f, bool wait, uint64_t
 }  // namespace
 
 namespace {
-// Workgroups of the two audit kernels (the scrub's verify, the fetch verify): 8 per CU, or at most
-// RMQ_AUDIT_WGS of them.
-uint32_t audit_wgs(const rmq_engine* e) {
-  const uint32_t wgs = std::max<uint32_t>(e->cu_count, 1u) * 8u;
-  return e->audit_wgs ? std::min(wgs, e->audit_wgs) : wgs;
-}
-
 // Issue a fetch into the next slot: its kernels on the pipeline stream, an event after them.
 int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t mem, uint8_t* out,
                 uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket, bool sync) {
@@ -2149,498 +2130,6 @@ int rmq_read_consumer_table(rmq_engine* e, uint32_t first, uint32_t n, uint64_t*
   if (rc) return rc;
   const size_t C = e->cfg.max_consumers;
   HIP_TRY(hipMemcpy(out, e->st.cons + (size_t)first * C, (size_t)n * C * 8, hipMemcpyDeviceToHost));
-  return RMQ_OK;
-}
-
-// The plan's scan and the result rows of a range of n partitions (rmq_scrub, rmq_repair).
-static int scrub_buffers(rmq_engine* e, uint32_t n) {
-  if (e->scrub_cap >= n) return RMQ_OK;
-  if (e->d_scrub_tbase) hipFree(e->d_scrub_tbase);
-  if (e->d_scrub_rows) hipFree(e->d_scrub_rows);
-  e->d_scrub_tbase = e->d_scrub_rows = nullptr;
-  e->scrub_cap = 0;
-  int rc = dalloc(&e->d_scrub_tbase, (size_t)n + 1);
-  if (!rc) rc = dalloc(&e->d_scrub_rows, (size_t)n * 4);
-  if (rc) return rc;
-  e->scrub_cap = n;
-  return RMQ_OK;
-}
-
-int rmq_scrub(rmq_engine* e, uint32_t first, uint32_t n, rmq_scrub_res* res) {
-  if (!e) return RMQ_EINVAL;
-  EngineLock g(e);
-  const uint32_t P = e->cfg.num_partitions;
-  if (first > P || n > P - first) return RMQ_ENOPART;
-  if (!n) return RMQ_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = drain(e);  // (fetches run on the pipeline stream: the drain waited for them too)
-  if (rc) return rc;
-  rc = scrub_buffers(e, n);
-  if (rc) return rc;
-  ScrubArgs a{};
-  a.st = e->st;
-  a.crc = e->d_crc;
-  a.tbase = e->d_scrub_tbase;
-  a.rows = e->d_scrub_rows;
-  a.first = first;
-  a.n = n;
-  hipEvent_t r0 = nullptr, r1 = nullptr;
-  if (e->profile) {  // kernel 2: an event before the plan to one after the verify
-    r0 = pool_event(e);
-    r1 = pool_event(e);
-    e->prof[2].push_back({r0, r1});
-    HIP_TRY(hipEventRecord(r0, e->main_s));
-  }
-  // the tasks are counted on the device (the plan), so the verify grid is a fixed few workgroups
-  // per CU whose waves stride over them
-  launch_scrub(a, audit_wgs(e), e->main_s);
-  HIP_TRY(hipGetLastError());
-  if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
-  rc = stream_wait(e->main_s);
-  if (rc) return rc;
-  std::vector<uint64_t> rows((size_t)n * 4);
-  HIP_TRY(hipMemcpy(rows.data(), e->d_scrub_rows, rows.size() * 8, hipMemcpyDeviceToHost));
-  bool corrupt = false;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint64_t key = rows[4ull * i];
-    corrupt = corrupt || key != kScrubClean;
-    if (!res) continue;
-    rmq_scrub_res& x = res[i];
-    std::memset(&x, 0, sizeof x);
-    x.records_ok = rows[4ull * i + 1];
-    x.bytes_ok = rows[4ull * i + 2];
-    x.replicas = (uint32_t)rows[4ull * i + 3];
-    x.bad_offset = key == kScrubClean ? RMQ_OFFSET_NONE : key >> 5;
-    x.bad_replica = key == kScrubClean ? 0u : (uint32_t)(key >> 2) & 7u;
-    x.bad_kind = key == kScrubClean ? 0u : (uint32_t)key & 3u;
-    x.status = key == kScrubClean ? RMQ_OK : RMQ_ECORRUPT;
-  }
-  return corrupt ? RMQ_ECORRUPT : RMQ_OK;
-}
-
-int rmq_repair(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags, rmq_repair_res* res) {
-  if (!e || (flags & ~RMQ_REPAIR_DRY_RUN)) return RMQ_EINVAL;
-  EngineLock g(e);
-  const uint32_t P = e->cfg.num_partitions, RF = e->cfg.replication_factor;
-  if (first > P || n > P - first) return RMQ_ENOPART;
-  if (!n) return RMQ_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = drain(e);
-  if (rc) return rc;
-  rc = scrub_buffers(e, n);
-  if (rc) return rc;
-  // a verdict per task: a partition has at most ring bytes / interval + 2 segments on each of its
-  // local slots, RF at the most
-  uint64_t tasks = 0;
-  for (uint32_t p = first; p < first + n; ++p)
-    tasks += RF * (((1ull << (e->ring[p] & 63ull)) >> e->st.interval_log2) + 2ull);
-  if (e->repair_verdict_cap < tasks) {
-    if (e->d_repair_verdict) hipFree(e->d_repair_verdict);
-    e->d_repair_verdict = nullptr;
-    e->repair_verdict_cap = 0;
-    rc = dalloc(&e->d_repair_verdict, (size_t)tasks);
-    if (rc) return rc;
-    e->repair_verdict_cap = tasks;
-  }
-  if (e->repair_counts_cap < n) {
-    if (e->d_repair_counts) hipFree(e->d_repair_counts);
-    e->d_repair_counts = nullptr;
-    e->repair_counts_cap = 0;
-    rc = dalloc(&e->d_repair_counts, (size_t)n * 3);
-    if (rc) return rc;
-    e->repair_counts_cap = n;
-  }
-  RepairArgs a{};
-  a.s.st = e->st;
-  a.s.crc = e->d_crc;
-  a.s.tbase = e->d_scrub_tbase;
-  a.s.rows = e->d_scrub_rows;
-  a.s.first = first;
-  a.s.n = n;
-  a.verdict = e->d_repair_verdict;
-  a.counts = e->d_repair_counts;
-  a.write = (flags & RMQ_REPAIR_DRY_RUN) ? 0u : 1u;
-  hipEvent_t r0 = nullptr, r1 = nullptr;
-  if (e->profile) {  // kernel 5: an event before the first plan to one after the last kernel of the call
-    r0 = pool_event(e);
-    r1 = pool_event(e);
-    e->prof[5].push_back({r0, r1});
-    HIP_TRY(hipEventRecord(r0, e->main_s));
-  }
-  // first pass: the scrub with a verdict per task
-  launch_repair_scan(a, audit_wgs(e), e->main_s);
-  HIP_TRY(hipGetLastError());
-  if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));  // (recorded again below if more kernels follow)
-  rc = stream_wait(e->main_s);
-  if (rc) return rc;
-  std::vector<uint64_t> rows((size_t)n * 4), counts((size_t)n * 3, 0);
-  HIP_TRY(hipMemcpy(rows.data(), e->d_scrub_rows, rows.size() * 8, hipMemcpyDeviceToHost));
-  bool corrupt = false;
-  for (uint32_t i = 0; i < n && !corrupt; ++i) corrupt = rows[4ull * i] != kScrubClean;
-  if (corrupt) {
-    // the repair kernel on the same plan, then (unless nothing may be written) the audit again
-    HIP_TRY(hipMemsetAsync(e->d_repair_counts, 0, counts.size() * 8, e->main_s));
-    launch_repair_copy(a, audit_wgs(e), e->main_s);
-    if (a.write) launch_scrub(a.s, audit_wgs(e), e->main_s);
-    HIP_TRY(hipGetLastError());
-    if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
-    rc = stream_wait(e->main_s);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(counts.data(), e->d_repair_counts, counts.size() * 8, hipMemcpyDeviceToHost));
-    if (a.write) HIP_TRY(hipMemcpy(rows.data(), e->d_scrub_rows, rows.size() * 8, hipMemcpyDeviceToHost));
-  }
-  corrupt = false;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint64_t key = rows[4ull * i];
-    corrupt = corrupt || key != kScrubClean;
-    if (!res) continue;
-    rmq_repair_res& x = res[i];
-    std::memset(&x, 0, sizeof x);
-    x.segments_repaired = counts[3ull * i];
-    x.bytes_repaired = counts[3ull * i + 1];
-    x.segments_unrepaired = counts[3ull * i + 2];
-    x.replicas = (uint32_t)rows[4ull * i + 3];
-    x.bad_offset = key == kScrubClean ? RMQ_OFFSET_NONE : key >> 5;
-    x.bad_replica = key == kScrubClean ? 0u : (uint32_t)(key >> 2) & 7u;
-    x.bad_kind = key == kScrubClean ? 0u : (uint32_t)key & 3u;
-    x.status = key == kScrubClean ? RMQ_OK : RMQ_ECORRUPT;
-  }
-  return corrupt ? RMQ_ECORRUPT : RMQ_OK;
-}
-
-// The repair's first pass, then the gaps, the walks and the install of reindex.hip on the same plan,
-// then (if an entry changed) the audit again.
-int rmq_reindex(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags, rmq_reindex_res* res) {
-  if (!e || (flags & ~(RMQ_REINDEX_DRY_RUN | RMQ_REINDEX_ALL))) return RMQ_EINVAL;
-  EngineLock g(e);
-  const uint32_t P = e->cfg.num_partitions, RF = e->cfg.replication_factor;
-  if (first > P || n > P - first) return RMQ_ENOPART;
-  if (!n) return RMQ_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = drain(e);
-  if (rc) return rc;
-  rc = scrub_buffers(e, n);
-  if (rc) return rc;
-  // the repair's task bound: a verdict per task, and a gap and a rebuilt entry per task at the most
-  // (a partition with a local slot has at least as many tasks as live entries plus one)
-  uint64_t tasks = 0;
-  for (uint32_t p = first; p < first + n; ++p)
-    tasks += RF * (((1ull << (e->ring[p] & 63ull)) >> e->st.interval_log2) + 2ull);
-  if (e->repair_verdict_cap < tasks) {
-    if (e->d_repair_verdict) hipFree(e->d_repair_verdict);
-    e->d_repair_verdict = nullptr;
-    e->repair_verdict_cap = 0;
-    rc = dalloc(&e->d_repair_verdict, (size_t)tasks);
-    if (rc) return rc;
-    e->repair_verdict_cap = tasks;
-  }
-  if (e->reindex_cap < tasks) {
-    if (e->d_reindex_gaps) hipFree(e->d_reindex_gaps);
-    if (e->d_reindex_scratch) hipFree(e->d_reindex_scratch);
-    e->d_reindex_gaps = e->d_reindex_scratch = nullptr;
-    e->reindex_cap = 0;
-    rc = dalloc(&e->d_reindex_gaps, (size_t)tasks * 2);
-    if (!rc) rc = dalloc(&e->d_reindex_scratch, (size_t)tasks * 2);
-    if (rc) return rc;
-    e->reindex_cap = tasks;
-  }
-  if (e->reindex_counts_cap < n) {
-    if (e->d_reindex_counts) hipFree(e->d_reindex_counts);
-    e->d_reindex_counts = nullptr;
-    e->reindex_counts_cap = 0;
-    rc = dalloc(&e->d_reindex_counts, (size_t)n * 3 + 1);
-    if (rc) return rc;
-    e->reindex_counts_cap = n;
-  }
-  ReindexArgs a{};
-  a.s.st = e->st;
-  a.s.crc = e->d_crc;
-  a.s.tbase = e->d_scrub_tbase;
-  a.s.rows = e->d_scrub_rows;
-  a.s.first = first;
-  a.s.n = n;
-  a.verdict = e->d_repair_verdict;
-  a.gaps = e->d_reindex_gaps;
-  a.scratch = e->d_reindex_scratch;
-  a.counts = e->d_reindex_counts;
-  a.ngaps = reinterpret_cast<uint32_t*>(e->d_reindex_counts + (size_t)n * 3);
-  a.cap = tasks;  // (>= n: every partition of the range adds at least 2 RF)
-  a.all = (flags & RMQ_REINDEX_ALL) ? 1u : 0u;
-  a.write = (flags & RMQ_REINDEX_DRY_RUN) ? 0u : 1u;
-  RepairArgs ra{};
-  ra.s = a.s;
-  ra.verdict = e->d_repair_verdict;
-  hipEvent_t r0 = nullptr, r1 = nullptr;
-  if (e->profile) {  // kernel 8: an event before the first plan to one after the last kernel of the call
-    r0 = pool_event(e);
-    r1 = pool_event(e);
-    e->prof[8].push_back({r0, r1});
-    HIP_TRY(hipEventRecord(r0, e->main_s));
-  }
-  std::vector<uint64_t> rows((size_t)n * 4), counts((size_t)n * 3, 0);
-  HIP_TRY(hipMemsetAsync(e->d_reindex_counts, 0, (counts.size() + 1) * 8, e->main_s));
-  launch_repair_scan(ra, audit_wgs(e), e->main_s);
-  launch_reindex(a, audit_wgs(e), e->main_s);
-  HIP_TRY(hipGetLastError());
-  if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));  // (recorded again below if the audit follows)
-  rc = stream_wait(e->main_s);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(rows.data(), e->d_scrub_rows, rows.size() * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(counts.data(), e->d_reindex_counts, counts.size() * 8, hipMemcpyDeviceToHost));
-  bool wrote = false;
-  for (uint32_t i = 0; i < n && !wrote; ++i) wrote = a.write && counts[3ull * i + 1] != 0;
-  if (wrote) {
-    launch_scrub(a.s, audit_wgs(e), e->main_s);
-    HIP_TRY(hipGetLastError());
-    if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
-    rc = stream_wait(e->main_s);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(rows.data(), e->d_scrub_rows, rows.size() * 8, hipMemcpyDeviceToHost));
-  }
-  bool corrupt = false;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint64_t key = rows[4ull * i];
-    corrupt = corrupt || key != kScrubClean;
-    if (!res) continue;
-    rmq_reindex_res& x = res[i];
-    std::memset(&x, 0, sizeof x);
-    x.entries_live = counts[3ull * i];
-    x.entries_rewritten = counts[3ull * i + 1];
-    x.gaps_unresolved = counts[3ull * i + 2];
-    x.replicas = (uint32_t)rows[4ull * i + 3];
-    x.bad_offset = key == kScrubClean ? RMQ_OFFSET_NONE : key >> 5;
-    x.bad_replica = key == kScrubClean ? 0u : (uint32_t)(key >> 2) & 7u;
-    x.bad_kind = key == kScrubClean ? 0u : (uint32_t)key & 3u;
-    x.status = key == kScrubClean ? RMQ_OK : RMQ_ECORRUPT;
-  }
-  return corrupt ? RMQ_ECORRUPT : RMQ_OK;
-}
-
-// rmq_repair's first pass and local copy, then the rounds over the transport (repair_remote.cpp),
-// then the audit again. Without a transport this is rmq_repair step by step.
-int rmq_repair_remote(rmq_engine* e, uint32_t first, uint32_t n, uint32_t flags, rmq_repair_remote_res* res,
-                      uint64_t* served) {
-  if (!e || (flags & ~RMQ_REPAIR_DRY_RUN)) return RMQ_EINVAL;
-  EngineLock g(e);
-  if (served) served[0] = served[1] = 0;
-  const uint32_t P = e->cfg.num_partitions, RF = e->cfg.replication_factor;
-  if (first > P || n > P - first) return RMQ_ENOPART;
-  if (!n && !e->repl) return RMQ_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = drain(e);  // (collective with a transport: a rank with n = 0 drains and serves too)
-  if (rc) return rc;
-  uint64_t tasks = 0;
-  for (uint32_t p = first; p < first + n; ++p)
-    tasks += RF * (((1ull << (e->ring[p] & 63ull)) >> e->st.interval_log2) + 2ull);
-  if (n) {
-    rc = scrub_buffers(e, n);
-    if (rc) return rc;
-    if (e->repair_verdict_cap < tasks) {
-      if (e->d_repair_verdict) hipFree(e->d_repair_verdict);
-      e->d_repair_verdict = nullptr;
-      e->repair_verdict_cap = 0;
-      rc = dalloc(&e->d_repair_verdict, (size_t)tasks);
-      if (rc) return rc;
-      e->repair_verdict_cap = tasks;
-    }
-    if (e->repair_counts_cap < n) {
-      if (e->d_repair_counts) hipFree(e->d_repair_counts);
-      e->d_repair_counts = nullptr;
-      e->repair_counts_cap = 0;
-      rc = dalloc(&e->d_repair_counts, (size_t)n * 3);
-      if (rc) return rc;
-      e->repair_counts_cap = n;
-    }
-  }
-  RepairArgs a{};
-  a.s.st = e->st;
-  a.s.crc = e->d_crc;
-  a.s.tbase = e->d_scrub_tbase;
-  a.s.rows = e->d_scrub_rows;
-  a.s.first = first;
-  a.s.n = n;
-  a.verdict = e->d_repair_verdict;
-  a.counts = e->d_repair_counts;
-  a.write = (flags & RMQ_REPAIR_DRY_RUN) ? 0u : 1u;
-  hipEvent_t r0 = nullptr, r1 = nullptr;
-  if (e->profile) {  // kernel 6: an event before the first plan to one after the last kernel of the call
-    r0 = pool_event(e);
-    r1 = pool_event(e);
-    e->prof[6].push_back({r0, r1});
-    HIP_TRY(hipEventRecord(r0, e->main_s));
-    HIP_TRY(hipEventRecord(r1, e->main_s));  // (recorded again after every later kernel)
-  }
-  std::vector<uint64_t> rows((size_t)n * 4), counts((size_t)n * 3, 0), fetched((size_t)n * 2, 0);
-  bool corrupt = false;
-  if (n) {
-    // pass 0: the scrub with a verdict per task, then rmq_repair's copy from a clean local slot
-    launch_repair_scan(a, audit_wgs(e), e->main_s);
-    HIP_TRY(hipGetLastError());
-    if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
-    rc = stream_wait(e->main_s);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(rows.data(), e->d_scrub_rows, rows.size() * 8, hipMemcpyDeviceToHost));
-    for (uint32_t i = 0; i < n && !corrupt; ++i) corrupt = rows[4ull * i] != kScrubClean;
-    if (corrupt) {
-      HIP_TRY(hipMemsetAsync(e->d_repair_counts, 0, counts.size() * 8, e->main_s));
-      launch_repair_copy(a, audit_wgs(e), e->main_s);
-      HIP_TRY(hipGetLastError());
-      if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
-    }
-  }
-  uint64_t sv[2] = {0, 0};
-  if (e->repl) {
-    rc = repair_remote_rounds(e, corrupt ? &a : nullptr, audit_wgs(e), tasks, fetched.data(), sv);
-    if (rc) return rc;
-    if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
-  }
-  if (served) served[0] = sv[0], served[1] = sv[1];
-  if (corrupt) {
-    if (a.write) launch_scrub(a.s, audit_wgs(e), e->main_s);
-    HIP_TRY(hipGetLastError());
-    if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
-    rc = stream_wait(e->main_s);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(counts.data(), e->d_repair_counts, counts.size() * 8, hipMemcpyDeviceToHost));
-    if (a.write) HIP_TRY(hipMemcpy(rows.data(), e->d_scrub_rows, rows.size() * 8, hipMemcpyDeviceToHost));
-  }
-  corrupt = false;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint64_t key = rows[4ull * i];
-    corrupt = corrupt || key != kScrubClean;
-    if (!res) continue;
-    rmq_repair_remote_res& x = res[i];
-    std::memset(&x, 0, sizeof x);
-    x.segments_repaired = counts[3ull * i];
-    x.bytes_repaired = counts[3ull * i + 1];
-    x.segments_fetched = fetched[2ull * i];
-    x.bytes_fetched = fetched[2ull * i + 1];
-    x.segments_unrepaired = counts[3ull * i + 2] - fetched[2ull * i];  // (a fetched pair had no local donor)
-    x.replicas = (uint32_t)rows[4ull * i + 3];
-    x.bad_offset = key == kScrubClean ? RMQ_OFFSET_NONE : key >> 5;
-    x.bad_replica = key == kScrubClean ? 0u : (uint32_t)(key >> 2) & 7u;
-    x.bad_kind = key == kScrubClean ? 0u : (uint32_t)key & 3u;
-    x.status = key == kScrubClean ? RMQ_OK : RMQ_ECORRUPT;
-  }
-  return corrupt ? RMQ_ECORRUPT : RMQ_OK;
-}
-
-// Host checks (restore_check.hpp), staging, then verify -> install -> finish on the pipeline stream
-// (restore.hip): the verdicts stay on the device between the passes and are read back once.
-int rmq_restore(rmq_engine* e, uint32_t n, const rmq_restore_item* items, uint32_t mem, const uint8_t* buf,
-                uint64_t buf_bytes, const uint64_t* rec_pos, uint64_t rec_words, uint32_t flags, rmq_restore_res* res) {
-  if (!e || (flags & ~RMQ_RESTORE_DRY_RUN) || (n && !items) || (mem != RMQ_MEM_HOST && mem != RMQ_MEM_DEVICE) ||
-      (buf_bytes && !buf) || (rec_words && !rec_pos) || (mem == RMQ_MEM_DEVICE && ((uintptr_t)buf & 15u)))
-    return RMQ_EINVAL;
-  EngineLock g(e);
-  if (e->repl) return RMQ_EINVAL;  // a restarted rank restores before it attaches
-  if (!n) return RMQ_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = drain(e);
-  if (rc) return rc;
-  const uint32_t P = e->cfg.num_partitions, RF = e->cfg.replication_factor;
-  // pristine: log start and end offsets and positions all 0 (the engine is drained: the current set)
-  std::vector<uint64_t> so(P), sp(P), eo(P), ep(P);
-  HIP_TRY(hipMemcpy(so.data(), e->st.start_off, (size_t)P * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(sp.data(), e->st.start_pos, (size_t)P * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(eo.data(), e->st.leo, (size_t)P * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(ep.data(), e->st.used, (size_t)P * 8, hipMemcpyDeviceToHost));
-  const RestorePlan pl = restore_plan(n, items, P, buf_bytes, rec_words, [&](uint32_t p) {
-    RestorePart q;
-    q.seg = 1ull << (e->ring[p] & 63ull);
-    q.pristine = !(so[p] | sp[p] | eo[p] | ep[p]);
-    q.local = false;
-    for (uint32_t r = 0; r < RF; ++r) q.local = q.local || e->ranks[(size_t)p * RF + r] == e->cfg.rank;
-    return q;
-  });
-  const uint32_t na = (uint32_t)pl.accepted.size();
-  std::vector<uint64_t> key(na, kScrubClean);
-  if (na) {
-    const bool host = mem == RMQ_MEM_HOST;
-    rmq_engine::Restore& B = e->rs;
-    if (B.items_cap < na) {  // the three per-item arrays share a capacity
-      uint64_t c0 = 0, c1 = 0, c2 = 0;
-      B.items_cap = 0;
-      rc = restore_grow(&B.items, &c0, na);
-      if (!rc) rc = restore_grow(&B.rbase, &c1, (uint64_t)na + 1);
-      if (!rc) rc = restore_grow(&B.key, &c2, na);
-      if (!rc) B.items_cap = na;
-    }
-    if (!rc) rc = restore_grow(&B.tab, &B.tab_cap, pl.tab_hi - pl.tab_lo);
-    if (!rc && host && pl.buf_hi > pl.buf_lo) rc = restore_grow(&B.buf, &B.buf_cap, pl.buf_hi - pl.buf_lo);
-    if (rc) return rc;
-    std::vector<RestoreItem> di(na);
-    for (uint32_t k = 0; k < na; ++k) {
-      const rmq_restore_item& it = items[pl.accepted[k]];
-      RestoreItem& d = di[k];
-      d.first_off = it.first_offset, d.first_pos = it.first_pos, d.count = it.count, d.bytes = it.bytes;
-      d.run = host ? B.buf + (it.bytes ? it.buf_pos - pl.buf_lo : 0ull) : buf + it.buf_pos;
-      d.tab = B.tab + (it.table_start - pl.tab_lo);
-      d.commit = it.commit;
-      d.pidx = it.pidx, d.pad = 0;
-    }
-    hipStream_t s = e->main_s;
-    HIP_TRY(hipMemcpyAsync(B.items, di.data(), (size_t)na * sizeof(RestoreItem), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(B.rbase, pl.rbase.data(), ((size_t)na + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(B.key, key.data(), (size_t)na * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(B.tab, rec_pos + pl.tab_lo, (size_t)(pl.tab_hi - pl.tab_lo) * 8, hipMemcpyHostToDevice, s));
-    if (host && pl.buf_hi > pl.buf_lo)
-      HIP_TRY(hipMemcpyAsync(B.buf, buf + pl.buf_lo, (size_t)(pl.buf_hi - pl.buf_lo), hipMemcpyHostToDevice, s));
-    RestoreArgs a{};
-    a.st = e->st;
-    a.sets[0] = e->sets[0];
-    a.sets[1] = e->sets[1];
-    a.crc = e->d_crc;
-    a.items = B.items;
-    a.rbase = B.rbase;
-    a.key = B.key;
-    a.n = na;
-    hipEvent_t r0 = nullptr, r1 = nullptr;
-    if (e->profile) {  // kernel 7: an event before the verify to one after the last kernel of the call
-      r0 = pool_event(e);
-      r1 = pool_event(e);
-      e->prof[7].push_back({r0, r1});
-      HIP_TRY(hipEventRecord(r0, s));
-    }
-    const uint64_t records = pl.rbase.back();
-    launch_restore_verify(a, records, audit_wgs(e), s);
-    if (!(flags & RMQ_RESTORE_DRY_RUN)) launch_restore_install(a, records, audit_wgs(e), s);
-    HIP_TRY(hipGetLastError());
-    if (e->profile) HIP_TRY(hipEventRecord(r1, s));
-    HIP_TRY(hipMemcpyAsync(key.data(), B.key, (size_t)na * 8, hipMemcpyDeviceToHost, s));
-    rc = stream_wait(s);  // (the caller's buffers are free again, and the rows can be written)
-    if (rc) return rc;
-  }
-  std::vector<int32_t> status = pl.status;
-  for (uint32_t k = 0; k < na; ++k)
-    if (key[k] != kScrubClean) status[pl.accepted[k]] = RMQ_ECORRUPT;
-  if (res) {
-    for (uint32_t i = 0; i < n; ++i) {
-      rmq_restore_res& x = res[i];
-      std::memset(&x, 0, sizeof x);
-      x.bad_offset = RMQ_OFFSET_NONE;
-      x.status = status[i];
-    }
-    for (uint32_t k = 0; k < na; ++k) {
-      rmq_restore_res& x = res[pl.accepted[k]];
-      if (key[k] == kScrubClean) {
-        x.records = items[pl.accepted[k]].count;
-        x.bytes = items[pl.accepted[k]].bytes;
-      } else {
-        x.bad_offset = key[k] >> 5;
-        x.bad_kind = (uint32_t)key[k] & 3u;
-      }
-    }
-  }
-  return restore_return(status);
-}
-
-int rmq_fault_corrupt_repair(rmq_engine* e, uint32_t dst, int64_t at) {
-  if (!e) return RMQ_EINVAL;
-  EngineLock g(e);
-  if (!e->repl || dst >= e->repl->world || dst == e->repl->rank) return RMQ_EINVAL;
-  e->rr.flip[dst] = true;
-  e->rr.flip_at[dst] = at;
   return RMQ_OK;
 }
 

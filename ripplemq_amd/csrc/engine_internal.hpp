@@ -1,6 +1,6 @@
 // engine_internal.hpp — the engine object shared by the host-side translation units
-// (engine.cpp: C-ABI, append pipeline, fetch, control, scrub, repair, restore; replication.cpp: replica-log rounds;
-// repair_remote.cpp: the rounds of rmq_repair_remote).
+// (engine.cpp: C-ABI, append pipeline, fetch, control; audit.cpp: scrub, repair, reindex, remote repair,
+// restore; replication.cpp: replica-log rounds; repair_remote.cpp: the rounds of rmq_repair_remote).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -416,22 +416,19 @@ struct rmq_engine {
   hipEvent_t prof_t0 = nullptr, prof_t1 = nullptr;
   bool prof_started = false, prof_ended = false;
   std::vector<EvPair> prof[9];
-  // rmq_scrub: the plan's scan and the result rows of the partitions of one call (grown on demand)
-  uint64_t* d_scrub_tbase = nullptr;
-  uint64_t* d_scrub_rows = nullptr;
-  uint32_t scrub_cap = 0;
-  // rmq_repair: a verdict byte per task of the first pass and the counters of the range's partitions
-  uint8_t* d_repair_verdict = nullptr;
-  uint64_t repair_verdict_cap = 0;
-  uint64_t* d_repair_counts = nullptr;
-  uint32_t repair_counts_cap = 0;
-  // rmq_reindex: the gap list and the rebuilt entries (a pair of words per task of the bound), the
-  // gap counter and the counters of the range's partitions
-  uint64_t* d_reindex_gaps = nullptr;
-  uint64_t* d_reindex_scratch = nullptr;
-  uint64_t reindex_cap = 0;
-  uint64_t* d_reindex_counts = nullptr;  // [n][3], then the gap counter's word
-  uint32_t reindex_counts_cap = 0;
+  // rmq_scrub, rmq_repair, rmq_repair_remote, rmq_reindex (audit.cpp): device buffers of one call's
+  // range of n partitions, grown on demand (a capacity in elements next to each)
+  struct Audit {
+    uint64_t* tbase = nullptr;    // [n + 1] the plan's scan
+    uint64_t* rows = nullptr;     // [n][4] the result rows
+    uint8_t* verdict = nullptr;   // [tasks of the bound] the first pass's verdicts
+    uint64_t* counts = nullptr;   // [n][3] the repair's counters
+    uint64_t* gaps = nullptr;     // [tasks][2] rmq_reindex: the gap list
+    uint64_t* scratch = nullptr;  // [tasks][2] rmq_reindex: the rebuilt entries
+    uint64_t* rcounts = nullptr;  // [n][3] rmq_reindex's counters, then the gap counter's word
+    uint64_t tbase_cap = 0, rows_cap = 0, verdict_cap = 0, counts_cap = 0, gaps_cap = 0, scratch_cap = 0,
+             rcounts_cap = 0;
+  } au;
   // rmq_repair_remote (repair_remote.cpp): device buffers grown on demand (a capacity next to each),
   // fixed control words with their page-locked mirror, the per-destination budget and the fault hook
   struct RemoteRepair {
@@ -541,8 +538,22 @@ int dalloc(T** p, size_t count) {
   return RMQ_OK;
 }
 
-// rmq_restore's device scratch: grown (never shrunk), RMQ_ENOMEM with the old buffer gone and
-// nothing else changed.
+// Grow a device buffer on demand (never shrunk) through dalloc: the fresh buffer zeroed and the device
+// synchronised, dalloc's code with the pointer null and the capacity 0 on failure.
+template <typename T>
+int grow(T** p, uint64_t* cap, uint64_t need) {
+  if (*cap >= need && *p) return RMQ_OK;
+  if (*p) hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  int rc = dalloc(p, (size_t)need);
+  if (rc) return rc;
+  *cap = need;
+  return RMQ_OK;
+}
+
+// rmq_restore's grow, which stages asynchronously right after it: no zeroing, no device-wide
+// synchronise, and every failure is RMQ_ENOMEM with the HIP error cleared and the old buffer gone.
 template <typename T>
 int restore_grow(T** p, uint64_t* cap, uint64_t need) {
   if (*cap >= need && *p) return RMQ_OK;
@@ -564,6 +575,26 @@ int drain(rmq_engine* e);
 int quiesce(rmq_engine* e);
 int check_err(rmq_engine* e);
 int event_wait(hipEvent_t ev);  // spin on queries (20 ms), then block
+int stream_wait(hipStream_t s);  // the same for everything issued on a stream
+hipEvent_t pool_event(rmq_engine* e);
+int fetch_flush(rmq_engine* e);
+// The engine lock of every call: held-back asynchronous fetches go to the pipeline stream first, so
+// whatever the call issues is ordered after them (their contract); a launch error stays sticky on the
+// stream and surfaces at the next check.
+struct EngineLock {
+  std::lock_guard<std::mutex> g;
+  explicit EngineLock(rmq_engine* e) : g(e->mu) {
+    if (!e->fpend.empty() && hipSetDevice(e->device) == hipSuccess) (void)fetch_flush(e);
+  }
+};
+// Workgroups of the audit kernels (the scrub's verify, the fetch verify): 8 per CU, or at most
+// RMQ_AUDIT_WGS of them.
+inline uint32_t audit_wgs(const rmq_engine* e) {
+  const uint32_t wgs = std::max<uint32_t>(e->cu_count, 1u) * 8u;
+  return e->audit_wgs ? std::min(wgs, e->audit_wgs) : wgs;
+}
+// audit.cpp
+void audit_free(rmq_engine* e);
 // replication.cpp
 int repl_attach(rmq_engine* e, Transport* t);
 void repl_free(rmq_engine* e);

@@ -1,6 +1,6 @@
 // repair_remote.cpp — the collective rounds of rmq_repair_remote (FORMAT.md §10 "Remote repair").
 //
-// After rmq_repair's first pass (engine.cpp) every rank plays RF - 1 rounds, the same sequence of
+// After rmq_repair's first pass (audit.cpp) every rank plays RF - 1 rounds, the same sequence of
 // Transport::exchange calls on each: round j asks candidate j of every partition for the pairs still
 // failing. A round is {request bytes, pairs that want a candidate} words all-to-all (every rank sees
 // every count: all stop together once all are zero), the request lists, the serve kernels on the
@@ -18,18 +18,6 @@
 namespace rmq {
 
 namespace {
-
-template <typename T>
-int grow(T** p, uint64_t* cap, uint64_t need) {
-  if (*cap >= need && *p) return RMQ_OK;
-  if (*p) hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  int rc = dalloc(p, (size_t)need);
-  if (rc) return rc;
-  *cap = need;
-  return RMQ_OK;
-}
 
 int swap_words(rmq_engine* e, uint32_t W, uint32_t me) {
   rmq_engine::RemoteRepair& B = e->rr;

@@ -191,6 +191,32 @@ def test_range_and_argument_errors(state1):
     U.assert_clean(e.scrub(), e, cfg)  # nothing was flipped
 
 
+def test_profile_regions_of_scrub_repair_reindex():
+    """rmq_profile_query's regions 2 (scrub), 5 (repair) and 8 (reindex): one pair of events per call,
+    from before its first kernel to after its last; a scrub inside another call adds none to 2."""
+    cfg = U.cfg1()
+    with Engine(cfg) as e:
+        U.fill1(e, 1)
+        e.profile(1)
+        e.scrub(), e.repair(), e.reindex()
+        assert (e.last_scrub_rc, e.last_repair_rc, e.last_reindex_rc) == (A.RMQ_OK,) * 3
+        first = {k: e.profile_query(k) for k in (2, 5, 8)}
+        print("one call each:", first)
+        for k, (calls, ms) in first.items():
+            assert calls == 1 and ms > 0, (k, calls, ms)
+        assert e.profile_query(6)[0] == 0 and e.profile_query(7)[0] == 0
+        S, p = cfg.segment_bytes, 0
+        rec = next(x for x in U.host_walk(e, cfg, 2, p)[2] if x[2] == 100)
+        e.fault_flip_ring(2, p, (rec[1] + 16 + 50) % S)  # a payload byte: the repair copies and scrubs again
+        row = e.repair()[p]
+        assert e.last_repair_rc == A.RMQ_OK and int(row["segments_repaired"]) == 1, row
+        calls, ms = e.profile_query(5)
+        print("second repair:", calls, ms)
+        assert calls == 2 and ms > first[5][1], (calls, ms, first[5])
+        assert e.profile_query(2)[0] == 1  # the repair's scrub is inside region 5
+        U.assert_clean(e.scrub(), e, cfg)
+
+
 def test_after_ring_move():
     cfg = U.cfg1(pool_bytes=16 * 4096)
     with Engine(cfg) as e:
