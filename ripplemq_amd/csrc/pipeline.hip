@@ -1540,8 +1540,15 @@ __device__ __forceinline__ TaskState stage3_r2(const PipeArgs& A, const TaskPos&
   }
   if (S.nblk) {
     // buffer loads through a descriptor of the span (bounds-checked: blocks past it read 0), one
-    // 32-bit offset for all four (the span base is wave-uniform)
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(S.sbase), 0, (int)(16u * S.nblk), 0x00020000);
+    // 32-bit offset for all four (the span base is wave-uniform). These loads are issued before the
+    // batch's verdict is known (cand), and a packed batch that stage 2 rejects (sum(len) over
+    // payload_bytes) has spans that run past the bytes its caller declared readable: the descriptor
+    // ends with the last block that holds a declared byte. A span of an accepted batch ends at or
+    // before it, so its loads are the same with and without the bound (kernel arguments only: no
+    // dependent load).
+    const u64 pend = (reinterpret_cast<u64>(b.payload) + b.payload_bytes + 15ull) & ~15ull;
+    const u32 span = pend > S.sbase ? (u32)min((u64)(16u * S.nblk), pend - S.sbase) : 0u;
+    const auto rs = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(S.sbase), 0, (int)span, 0x00020000);
     const u32 vo = 16u * (threadIdx.x & 63u);
 #pragma unroll
     for (u32 u = 0; u < kSpanPer; ++u) {

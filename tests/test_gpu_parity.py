@@ -343,6 +343,35 @@ def test_stage3_roles_mixed_sizes(oracle_mod, monkeypatch, roles):
         assert max(ora.state(p)["log_start_offset"] for p in range(300)) > 0, "scenario must exercise retention"
 
 
+VARIANT_MODES = [({"RMQ_S3_STAGE": "0"}, 300), ({"RMQ_S3_PAIR": "1"}, 300), ({"RMQ_PRIO": "0"}, 300),
+                 ({"RMQ_S2_WGS": "1"}, 300), ({"RMQ_S2_WGS": "3"}, 300), ({"RMQ_AHEAD": "1"}, 300),
+                 ({"RMQ_RANK": "1"}, 8), ({"RMQ_RANK": "1"}, 300), ({"RMQ_STEAL": "1"}, 300)]
+
+
+@pytest.mark.parametrize("env,P", VARIANT_MODES,
+                         ids=[f"{k}={v}-P{P}" for e, P in VARIANT_MODES for k, v in e.items()])
+def test_variant_modes_small(oracle_mod, monkeypatch, env, P):
+    # the kernel variants DESIGN.md §5.3 keeps as valid (read at rmq_create), each on the scenario of
+    # test_stage3_roles_mixed_sizes shrunk: records of 0 B to 3 KB (image tasks, piecewise tasks,
+    # large-record waves) in launch groups of 4, a no-space batch, a partition not led, unknown
+    # partitions. RMQ_RANK=1 (stage1_tile_hash) with one key pass (P = 8) and two (P = 300).
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    cfg, dev, ora = pair(oracle_mod, num_partitions=P, replication_factor=3, segment_bytes=1 << 18,
+                         index_interval=256, max_batch_records=4096, pipeline_depth=4)
+    with dev, ora:
+        for e in (dev, ora):
+            e.set_replicas(9 % P, [1, 0, 2], 0)
+        mixed = StreamSpec(P, 3000, "uniform", size=(0, 3000), config_index=34, invalid_frac=0.005)
+        batches = [make_batch(mixed, b) for b in range(6)]
+        nsp = make_batch(StreamSpec(P, 3000, "uniform", size=100, config_index=33), 0)
+        nsp.pidx[:2500] = 5  # 2500 x 128 B > ring - I: partition 5 takes none of this batch's records
+        batches.insert(3, nsp)
+        _pipelined(dev, ora, batches)
+        compare_state(dev, ora, cfg, full_rings=True)
+        assert dev.state(9 % P)["log_end_offset"] == 0 and ora.state(5)["log_end_offset"] > 0
+
+
 def test_config_B_pipelined(oracle_mod):
     # BASELINE configs[2] batches submitted back to back in groups of 4
     cfg, dev, ora = pair(oracle_mod, num_partitions=4096, replication_factor=3, segment_bytes=1 << 24,
