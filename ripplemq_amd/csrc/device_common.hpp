@@ -45,6 +45,7 @@ __host__ __device__ __forceinline__ constexpr u32 record_bytes(u32 len) {
 }
 
 typedef u32 u32x4 __attribute__((ext_vector_type(4)));
+typedef u32 u32x2 __attribute__((ext_vector_type(2)));
 
 // 16-byte log store. RMQ_RING_NT=1: non-temporal (streams past L2, nothing left dirty for the
 // end-of-kernel writeback); 0: default policy.
@@ -62,6 +63,19 @@ __device__ __forceinline__ uint4 load_payload16(const void* src) {
 #else
   return *reinterpret_cast<const uint4*>(src);
 #endif
+}
+
+// The same load as a global one, for the append kernel's issue blocks. An append payload is device
+// or page-locked host memory, never LDS or scratch; the compiler counts a global load exactly,
+// while beside a pending flat load it turns every counted wait into vmcnt(0).
+typedef __attribute__((address_space(1))) const u32x4 gu32x4c;
+__device__ __forceinline__ uint4 load_payload16g(u64 addr) {
+#if RMQ_PAYLOAD_NT
+  const u32x4 x = __builtin_nontemporal_load((gu32x4c*)addr);
+#else
+  const u32x4 x = *(gu32x4c*)addr;
+#endif
+  return make_uint4(x[0], x[1], x[2], x[3]);
 }
 
 __device__ __forceinline__ void store_log16(uint8_t* dst, uint4 v) {
@@ -127,6 +141,33 @@ __device__ __forceinline__ void crc_nib_lds(const CrcConsts* crc, u32* scratch) 
   if (threadIdx.x < 128u)
     reinterpret_cast<uint4*>(scratch)[threadIdx.x] = reinterpret_cast<const uint4*>(&crc->nib[0][0])[threadIdx.x];
   __syncthreads();
+}
+// The same copy with its load and its LDS write apart, for a caller that issues the load beside
+// other loads and waits for all of them once (the caller holds the barrier before crc_expand_lds).
+// The threads after the nibble blocks also fetch the two pad-removal tables, inv_pad and inv_pad16
+// (four 16-byte blocks each), which crc_nib_put writes to `pads` ([2][16], kept after the barrier).
+constexpr u32 kNibBlocks = 128u, kPadBlocks = 4u;
+template <u32 kThreads>
+__device__ __forceinline__ uint4 crc_nib_load(const CrcConsts* crc) {
+  static_assert(sizeof(CrcConsts::nib) == kNibBlocks * 16 && kThreads >= kNibBlocks + 2u * kPadBlocks, "one block per thread");
+  static_assert(sizeof(CrcConsts::inv_pad) == kPadBlocks * 16 && sizeof(CrcConsts::inv_pad16) == kPadBlocks * 16, "pad tables");
+  const u32 t = threadIdx.x;
+  uint4 v = make_uint4(0, 0, 0, 0);
+  if (t < kNibBlocks + 2u * kPadBlocks) {
+    const uint4* src = t < kNibBlocks ? reinterpret_cast<const uint4*>(&crc->nib[0][0]) + t
+                       : t < kNibBlocks + kPadBlocks
+                           ? reinterpret_cast<const uint4*>(&crc->inv_pad[0]) + (t - kNibBlocks)
+                           : reinterpret_cast<const uint4*>(&crc->inv_pad16[0]) + (t - kNibBlocks - kPadBlocks);
+    v = *src;
+  }
+  return v;
+}
+__device__ __forceinline__ void crc_nib_put(u32* scratch, u32* pads, uint4 v) {
+  const u32 t = threadIdx.x;
+  if (t < kNibBlocks)
+    reinterpret_cast<uint4*>(scratch)[t] = v;
+  else if (t < kNibBlocks + 2u * kPadBlocks)
+    reinterpret_cast<uint4*>(pads)[t - kNibBlocks] = v;
 }
 template <u32 kThreads>
 __device__ __forceinline__ void crc_expand_lds(u32* tabs, const u32* scratch) {

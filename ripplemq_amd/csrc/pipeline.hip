@@ -100,6 +100,7 @@ struct Stage3Smem {
   u32 z[2][4][256];     // register shift past 16 and 32 zero bytes
   uint4 img[kPW][kTaskRecs][8];  // per wave: the task's records as laid out in the log (<= 128 B each)
   uint4 info[kPW][kTaskRecs];    // per wave: {pos lo, pos hi, p, lm | m << 8 | ok << 16 | dead << 24}
+  u32 pad[2][16];       // CrcConsts::inv_pad and inv_pad16 (a lane pair's halves of the pad removal)
   union {
     // single-GPU kernel: the register shift past 1024 zero bytes of the large-record waves (the
     // kernel with a transport reads it from global memory, L1/L2-resident: with 256-thread
@@ -114,6 +115,7 @@ struct Stage3Smem {
 
 constexpr size_t kSmemBytes = sizeof(Stage1Smem) > sizeof(Stage3Smem) ? sizeof(Stage1Smem) : sizeof(Stage3Smem);
 static_assert(kSmemBytes >= kMaxTiles * sizeof(u64), "stage 2's tile bases fit the dynamic LDS");
+static_assert(kPT != 256 || 4 * kSmemBytes <= 160 * 1024, "four 256-thread workgroups per CU fit the 160 KB of LDS");
 
 __device__ __forceinline__ u64 wave_incl_scan_u64(u64 v) { return wave_incl_scan<u64>(v); }
 
@@ -1391,6 +1393,7 @@ struct TaskRec {  // round 1: the record (the same words in both lanes of its pa
   u32 p, L;
   uint2 cr;
   u64 src;        // payload address
+  u32 rej;        // its batch's verdict (PipeScratch::binfo reject flags; wave-uniform)
 };
 
 // Where a task's records live: its batch in the group and the first record's index in the batch
@@ -1428,32 +1431,58 @@ constexpr u32 kSpanPer = 4;  // blocks per lane: spans of up to 4 KB (32 records
 #define RMQ_SPAN_AUX 2  // the span loads' cache policy: nt (read once per launch, like load_payload16)
 #endif
 
-// Record i of batch jb of the group in stage 3 (every lane: its own record, or its pair's).
+// A bounds-checked view of n elements of caller memory: a load past the n-th element returns 0 and
+// touches no memory, so lanes without a record issue the same instruction as the others and no
+// lane reads a byte its caller did not declare (a null base with n = 0 reads nothing at all).
+typedef __amdgpu_buffer_rsrc_t BufRsrc;
+__device__ __forceinline__ BufRsrc caller_view(const void* base, u32 bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
+}
+
+// Record i of batch jb of the group in stage 3 (every lane: its own record, or its pair's). Round
+// 1 of the task's loads, one issue block: every address is computed first and every load has its
+// own registers, so the wave waits once for all of them.
+//  * caller memory (pidx, len, payload_off) through bounds-checked views of the batch's n records;
+//    a packed batch has no payload_off and its view is empty
+//  * the engine's scratch (crank, pre, tile_base, binfo) on an index clamped into the arrays, the
+//    lane's values selected afterwards; both forms of the payload offset are issued, the batch's
+//    form (wave-uniform) chosen once the words are there
 __device__ __forceinline__ TaskRec stage3_r1_at(const PipeArgs& A, u32 jb, u32 i) {
   const PipeGroup& G = A.g3;
   const PipeScratch& x = A.s3;
   const PipeBatch& b = G.b[jb];
+  const u32 n = b.n;
+  const u64* const poff = b.poff;
+  const u64 pay = reinterpret_cast<u64>(b.payload);
+  const bool in = i < n;
+  const u64 gi = in ? (u64)G.tile0[jb] * kTR + i : 0ull;  // group record slot (0: any valid slot)
+  const BufRsrc vp = caller_view(b.pidx, 4u * n), vl = caller_view(b.len, 4u * n);
+  const BufRsrc vo = caller_view(poff, poff ? 8u * n : 0u);
+  const uint2* const pcr = x.crank + gi;
+  const u32* const ppre = x.pre + gi;
+  const u64* const ptb = x.tile_base + gi / kTR;
+  const u64* const prej = x.binfo + jb * 4;
+  __builtin_amdgcn_sched_barrier(0);
+  const u32 p = __builtin_amdgcn_raw_buffer_load_b32(vp, 4u * i, 0, 0);
+  const u32 L = __builtin_amdgcn_raw_buffer_load_b32(vl, 4u * i, 0, 0);
+  const u32x2 po = __builtin_amdgcn_raw_buffer_load_b64(vo, 8u * i, 0, 0);
+  const uint2 cr = *pcr;
+  const u32 pre = *ppre;
+  const u64 tb = *ptb;
+  const u32 rej = (u32)*prej;
+  __builtin_amdgcn_sched_barrier(0);
   TaskRec r;
-  r.p = 0u;
-  r.L = 0u;
-  r.cr = make_uint2(kFlJunk << kFlagShift, 0u);
-  r.src = reinterpret_cast<u64>(b.payload);
-  if (i < b.n) {
-    const u64 gi = (u64)G.tile0[jb] * kTR + i;  // group record slot
-    r.p = b.pidx[i];
-    r.L = b.len[i];
-    r.cr = x.crank[gi];
-    r.src += b.poff ? b.poff[i] : x.tile_base[gi / kTR] + x.pre[gi];
-  }
+  r.p = p;
+  r.L = L;
+  r.cr = in ? cr : make_uint2(kFlJunk << kFlagShift, 0u);
+  r.src = pay + (!in ? 0ull : poff ? ((u64)po[1] << 32) | po[0] : tb + pre);
+  r.rej = __builtin_amdgcn_readfirstlane(rej);
   return r;
 }
 __device__ __forceinline__ TaskRec stage3_r1(const PipeArgs& A, const TaskPos& T) { return stage3_r1_at(A, T.jb, task_rec(T)); }
 
-__device__ __forceinline__ u32 batch_rej(const PipeArgs& A, u32 jb) { return (u32)A.s3.binfo[jb * 4]; }
-__device__ __forceinline__ u32 batch_rej(const PipeArgs& A, const TaskPos& T) { return batch_rej(A, T.jb); }
-
 __device__ __forceinline__ bool stage3_cand_at(const PipeArgs& A, u32 jb, u32 i, const TaskRec& R) {
-  return i < A.g3.b[jb].n && (R.cr.x >> kFlagShift) == 0u && batch_rej(A, jb) == 0u;
+  return i < A.g3.b[jb].n && (R.cr.x >> kFlagShift) == 0u && R.rej == 0u;
 }
 __device__ __forceinline__ bool stage3_cand(const PipeArgs& A, const TaskPos& T, const TaskRec& R) {
   return stage3_cand_at(A, T.jb, task_rec(T), R);
@@ -1469,36 +1498,42 @@ __device__ __forceinline__ void round_blocks(const PipeArgs& A, const TaskRec& R
   for (u32 q = 0; q < kBL; ++q) {
     const u64 blk_addr = a0 + 16ull * (kPR * c + j + 2u * q);
     blk[q] = make_uint4(0, 0, 0, 0);
-    if (live && blk_addr < lim && !(A.debug & 4u)) blk[q] = load_payload16(reinterpret_cast<const void*>(blk_addr));
+    if (live && blk_addr < lim && !(A.debug & 4u)) blk[q] = load_payload16g(blk_addr);
   }
 }
 
-// The words of record i's partition state that place it (one round of gathers; lanes without a
-// candidate record load nothing).
+// The words of record i's partition state that place it: one round of gathers, as loaded. They are
+// the engine's own scratch, so every lane loads (a lane without a candidate record reads cell 0 and
+// partition 0 and discards them in rec_words): nothing waits on a lane's predicate.
+struct RecRaw {
+  uint4 a, b, c;  // the partition's words in one 64-byte line (stage 2 wrote them)
+  u64 ex;
+};
+__device__ __forceinline__ RecRaw rec_raw(const PipeArgs& A, u32 jb, u32 i, u32 p, bool cand) {
+  const u32 pc = cand ? p : 0u;
+  const u32 t = cand ? A.g3.tile0[jb] + i / kTR : 0u;
+  const u64* const pex = A.s3.excl + ((u64)pc * A.gt + t);
+  const uint4* const pk = reinterpret_cast<const uint4*>(A.s3.pk + (u64)pc * 8);
+  RecRaw w;
+  w.ex = *pex;
+  w.a = pk[0];
+  w.b = pk[1];
+  w.c = pk[2];
+  return w;
+}
 struct RecWords {
   u64 ex, tot, leo, used, rdesc;
   u32 lead, lm;
 };
-__device__ __forceinline__ RecWords rec_words(const PipeArgs& A, u32 jb, u32 i, u32 p, bool cand) {
-  const DevState& st = A.st;
+__device__ __forceinline__ RecWords rec_words(const RecRaw& w, bool cand) {
   RecWords W;
-  W.ex = W.tot = W.leo = W.used = 0ull;
-  W.rdesc = 8ull;  // any valid descriptor (a 256-byte ring at 0) for lanes that store nothing
-  W.lead = W.lm = 0u;
-  if (cand) {
-    const u32 t = A.g3.tile0[jb] + i / kTR;
-    W.ex = A.s3.excl[(u64)p * A.gt + t];
-    // the partition's words in one 64-byte line (stage 2 wrote them): three 16-byte loads
-    const uint4* pk = reinterpret_cast<const uint4*>(A.s3.pk + (u64)p * 8);
-    const uint4 a = pk[0], b = pk[1], c = pk[2];
-    W.leo = ((u64)a.y << 32) | a.x;
-    W.used = ((u64)a.w << 32) | a.z;
-    W.tot = ((u64)b.y << 32) | b.x;
-    W.rdesc = ((u64)b.w << 32) | b.z;
-    W.lead = c.x & 0xFFu;
-    W.lm = c.x >> 8;
-    (void)st;
-  }
+  W.ex = cand ? w.ex : 0ull;
+  W.leo = cand ? ((u64)w.a.y << 32) | w.a.x : 0ull;
+  W.used = cand ? ((u64)w.a.w << 32) | w.a.z : 0ull;
+  W.tot = cand ? ((u64)w.b.y << 32) | w.b.x : 0ull;
+  W.rdesc = cand ? ((u64)w.b.w << 32) | w.b.z : 8ull;  // 8: any valid descriptor (a 256-byte ring at 0) for lanes that store nothing
+  W.lead = cand ? w.c.x & 0xFFu : 0u;
+  W.lm = cand ? w.c.x >> 8 : 0u;
   return W;
 }
 
@@ -1516,15 +1551,21 @@ __device__ __forceinline__ void rec_place(const RecWords& W, const TaskRec& R, u
   lmo = W.lm | (W.lead ? kLead : 0u) | ((W.ex & kExclNoSpace) ? kNoSpace : 0u);
 }
 
+// The record's place from its partition words, once they are there (the first use of round 2).
+__device__ __forceinline__ void stage3_place(TaskState& S, const RecRaw& raw, const TaskRec& R, bool cand) {
+  const RecWords W = rec_words(raw, cand);
+  S.rdesc = W.rdesc;
+  if (cand) rec_place(W, R, S.pos, S.off, S.dead, S.lm, S.rk, S.rel16);
+}
+
 __device__ __forceinline__ TaskState stage3_r2(const PipeArgs& A, const TaskPos& T, const TaskRec& R, bool cand,
-                                               bool stage = false, RecWords* defer = nullptr) {
+                                               bool stage = false, RecRaw* defer = nullptr) {
   TaskState S;
   S.pos = S.off = 0ull;
   S.lm = S.dead = S.rel16 = S.rk = 0u;
   S.nblk = 0u;
   S.sbase = 0ull;
-  const RecWords W = rec_words(A, T.jb, task_rec(T), R.p, cand);
-  S.rdesc = W.rdesc;
+  S.rdesc = 8ull;
   // first round of payload blocks, speculatively (leadership is checked before any store): the
   // task's whole span by coalesced loads when it is packed and fits, else the lane pair's blocks
   const PipeBatch& b = A.g3.b[T.jb];
@@ -1538,6 +1579,13 @@ __device__ __forceinline__ TaskState stage3_r2(const PipeArgs& A, const TaskPos&
       S.sbase = s0;
     }
   }
+  // round 2 of the task's loads, one issue block: the lane pair's payload blocks (a task without a
+  // staged span), the partition words, the staged span; nothing waits for one before the next is
+  // issued. (The pair's blocks come first: placed after the span loads, the compiler made them wait
+  // for registers it shares with those.)
+  S.blk[kBL - 1] = make_uint4(0, 0, 0, 0);
+  if (!S.nblk) round_blocks(A, R, 0u, cand, S.blk);
+  const RecRaw W = rec_raw(A, T.jb, task_rec(T), R.p, cand);
   if (S.nblk) {
     // buffer loads through a descriptor of the span (bounds-checked: blocks past it read 0), one
     // 32-bit offset for all four (the span base is wave-uniform). These loads are issued before the
@@ -1555,14 +1603,12 @@ __device__ __forceinline__ TaskState stage3_r2(const PipeArgs& A, const TaskPos&
       const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(rs, vo + 1024u * u, 0, RMQ_SPAN_AUX);
       S.blk[u] = make_uint4(x[0], x[1], x[2], x[3]);
     }
-    S.blk[kBL - 1] = make_uint4(0, 0, 0, 0);
-  } else {
-    round_blocks(A, R, 0u, cand, S.blk);
   }
+  __builtin_amdgcn_sched_barrier(0);
   if (defer)
-    *defer = W;  // placed by the caller (rec_place) after work that does not wait for these loads
-  else if (cand)
-    rec_place(W, R, S.pos, S.off, S.dead, S.lm, S.rk, S.rel16);
+    *defer = W;  // placed by the caller (stage3_place) after work that does not wait for these loads
+  else
+    stage3_place(S, W, R, cand);
   return S;
 }
 
@@ -1587,11 +1633,11 @@ __device__ __forceinline__ void big_round(u64 src, u32 L, u32 k0, u32 ph, uint4 
   for (u32 u = 0; u < kBU; ++u) {
     const int jb = (int)(64u * (k0 + u) + lane) - (int)ph;
     const u64 ad = a0 + 16ll * jb;
-    b0[u] = jb >= 0 && ad < lim ? load_payload16(reinterpret_cast<const void*>(ad)) : make_uint4(0, 0, 0, 0);
+    b0[u] = jb >= 0 && ad < lim ? load_payload16g(ad) : make_uint4(0, 0, 0, 0);
   }
   tail = make_uint4(0, 0, 0, 0);
   const u64 ad = a0 + 16ull * (64u * (k0 + kBU) - ph);
-  if (sa && lane == 63u && ad < lim) tail = load_payload16(reinterpret_cast<const void*>(ad));
+  if (sa && lane == 63u && ad < lim) tail = load_payload16g(ad);
 }
 
 // The destination phase of a large record at ring position pos: its payload pieces start at piece
@@ -1803,7 +1849,7 @@ __device__ __forceinline__ void stage3_finish(const PipeArgs& A, const Stage3Sme
   const bool in = i < b.n;
   const u32 p = R.p, L = R.L;
   const u32 fl = R.cr.x >> kFlagShift;
-  const u32 rej = batch_rej(A, T);
+  const u32 rej = R.rej;
   const bool ns = (Z.lm & kNoSpace) != 0u;  // the record's (batch, partition) is over its limit
   const bool lead = (Z.lm & kLead) != 0u;
   const u32 lm8 = Z.lm & 0xFFu;
@@ -1908,8 +1954,9 @@ __device__ __forceinline__ void stage3_finish(const PipeArgs& A, const Stage3Sme
   u32 part = 0;
   if (okp && L) {
     const u32 pad = 16u * m - L;
-    part = pad ? gf2_mulmod_half(j ? acc & 0xFFFFu : acc >> 16, j ? A.crc->inv_pad16[pad] : A.crc->inv_pad[pad])
-               : (j ? 0u : acc);
+    // (the pad tables are in LDS since the wave's first round of loads: no global load between the
+    // CRC and the stores)
+    part = pad ? gf2_mulmod_half(j ? acc & 0xFFFFu : acc >> 16, S.pad[j][pad]) : (j ? 0u : acc);
   }
   part ^= pair_swap(part);
   uint4 h = make_uint4(0, 0, 0, 0);
@@ -2186,7 +2233,7 @@ __device__ __forceinline__ void stage3_build(const PipeArgs& A, Stage3RSmem& S, 
   const bool in = i < b.n;
   const u32 L = R.L;
   const u32 fl = R.cr.x >> kFlagShift;
-  const u32 rej = batch_rej(A, T);
+  const u32 rej = R.rej;
   const bool ns = (Z.lm & kNoSpace) != 0u;
   const bool lead = (Z.lm & kLead) != 0u;
   const u32 lm8 = Z.lm & 0xFFu;
@@ -2404,6 +2451,18 @@ __device__ __forceinline__ void stage3_roles(const PipeArgs& A, Stage3RSmem& S, 
 #ifndef RMQ_PIPE_WAVES_PER_SIMD
 #define RMQ_PIPE_WAVES_PER_SIMD 4  // <= 128 VGPRs, no spills: 2 resident workgroups per CU
 #endif
+// Wave-uniform values read from the kernel arguments, forced into scalar registers at this point:
+// the reads of one call are issued together and waited for once, where otherwise each is issued in
+// the block that first uses it and the wave pays a scalar-cache round trip per field.
+template <typename T>
+__device__ __forceinline__ void sgpr_fetch1(const T& v) {
+  asm volatile("" ::"s"(v));
+}
+template <typename... T>
+__device__ __forceinline__ void sgpr_fetch(const T&... v) {
+  (sgpr_fetch1(v), ...);
+}
+
 // Stage 1 of the launch's group, tile by tile: a static share (tiles wg, wg + wg1, ...) or, with
 // RMQ_STEAL, tiles taken from the group's counter (s1.nbig[1]) by the dedicated stage-1 workgroups
 // and by stage-3 workgroups that ran out of tasks, so ranking starts as soon as stage 3 frees a
@@ -2493,7 +2552,15 @@ __global__ __launch_bounds__(kPT, RMQ_PIPE_WAVES_PER_SIMD) void pipeline_kernel(
   }
   Stage3Smem& S = *reinterpret_cast<Stage3Smem*>(smem_raw);
   const PipeGroup& G = A.g3;
-  const u32 tasks = G.task0[G.nb];
+  // the prologue's wave-uniform arguments in two batches, each waited for once: here the fields at
+  // fixed places (the group's task table and the launch shape), below the task's batch and the
+  // scratch arrays of round 1 once the batch's index is known
+  sgpr_fetch(G.nb, G.task0[0], G.task0[1], G.task0[2], G.task0[3], G.task0[4], G.task0[5], G.task0[6], G.task0[7],
+             G.task0[8], A.s3_xcd, A.s3_lead, A.s3_roles, A.s3_pair);
+  static_assert(kMaxGroup == 8, "the task table's entries above");
+  u32 tasks = G.task0[0];  // task0[nb], from the entries already here
+#pragma unroll
+  for (u32 k = 1; k <= kMaxGroup; ++k) tasks = G.nb == k ? G.task0[k] : tasks;
   const u32 lane = threadIdx.x & 63;
   // the task index is wave-uniform: keep it (and the batch lookups) in scalar registers
   // (RMQ_S3_XCD: the stage-3 workgroups of one XCD take one contiguous range of slots, so records
@@ -2514,8 +2581,13 @@ __global__ __launch_bounds__(kPT, RMQ_PIPE_WAVES_PER_SIMD) void pipeline_kernel(
     const u32 tb = task + A.wg3 * kPW;
     const bool ha = task < tasks, hb = tb < tasks;  // (wave-uniform)
     const TaskPos Ta = task_pos(G, ha ? task : 0u), Tb = task_pos(G, hb ? tb : 0u);
+    const uint4 nv = crc_nib_load<kPT>(A.crc);
     const TaskRec Ra = stage3_r1(A, Ta), Rb = stage3_r1(A, Tb);
-    if (!(A.debug & 8u)) crc_tables_lds<kPT>(A.crc, &S.t8[0][0], reinterpret_cast<u32*>(&S.img[0][0][0]));
+    if (!(A.debug & 8u)) {
+      crc_nib_put(reinterpret_cast<u32*>(&S.img[0][0][0]), &S.pad[0][0], nv);
+      __syncthreads();
+      crc_expand_lds<kPT>(&S.t8[0][0], reinterpret_cast<const u32*>(&S.img[0][0][0]));
+    }
     const bool ca = ha && stage3_cand(A, Ta, Ra), cb = hb && stage3_cand(A, Tb, Rb);
     const TaskState Za = stage3_r2(A, Ta, Ra, ca);
     const TaskState Zb = stage3_r2(A, Tb, Rb, cb);
@@ -2531,19 +2603,27 @@ __global__ __launch_bounds__(kPT, RMQ_PIPE_WAVES_PER_SIMD) void pipeline_kernel(
     }
     return;
   }
-  // first task: its record and state/payload loads are in flight while the CRC tables fill LDS
+  // first task, round 1: the thread's block of the nibble and pad tables with the record words and
+  // the batch's verdict, one wait for all of it
   TaskPos T = task_pos(G, task < tasks ? task : 0u);
+  {
+    const PipeBatch& b = G.b[T.jb];
+    sgpr_fetch(b.pidx, b.len, b.poff, b.payload, b.n, G.tile0[T.jb], A.s3.crank, A.s3.pre, A.s3.tile_base, A.s3.binfo);
+  }
+  const uint4 nv = crc_nib_load<kPT>(A.crc);
   TaskRec R = stage3_r1(A, T);
-  // the slicing and zero-shift tables (contiguous in Stage3Smem) from their nibble tables, through
-  // the image area (first written after the barrier below); the expansion runs while the record's
-  // state and payload loads are in flight
+  // the slicing and zero-shift tables (contiguous in Stage3Smem) are expanded from their nibble
+  // tables through the image area (first written after the second barrier below). The nibble blocks
+  // go to LDS, round 2 (partition words, excl cell, payload) is issued, and only then does the
+  // workgroup take the barrier and expand: the table build runs while round 2 is in flight
   static_assert(offsetof(Stage3Smem, z) == sizeof(S.t8), "t8 and z adjacent in LDS");
-  if (!(A.debug & 8u)) crc_nib_lds<kPT>(A.crc, reinterpret_cast<u32*>(&S.img[0][0][0]));
+  if (!(A.debug & 8u)) crc_nib_put(reinterpret_cast<u32*>(&S.img[0][0][0]), &S.pad[0][0], nv);
   bool cand = task < tasks && stage3_cand(A, T, R);
-  RecWords W0;
+  RecRaw W0;
   TaskState Z = stage3_r2(A, T, R, cand, A.s3_stage != 0u, &W0);
+  __syncthreads();
   if (!(A.debug & 8u)) crc_expand_lds<kPT>(&S.t8[0][0], reinterpret_cast<const u32*>(&S.img[0][0][0]));
-  if (cand) rec_place(W0, R, Z.pos, Z.off, Z.dead, Z.lm, Z.rk, Z.rel16);
+  stage3_place(Z, W0, R, cand);
   __syncthreads();
   PIPE_STAMP(1);
   while (task < tasks) {
