@@ -177,7 +177,8 @@ typedef struct rmq_fetch_res {
   uint32_t bytes;              /* bytes of the returned records (FORMAT.md record layout) */
   int32_t status;              /* RMQ_OK, RMQ_ENOTLEADER, RMQ_ENOPART, RMQ_EINVAL, RMQ_EOFFSET, RMQ_ENOSPC,
                                   RMQ_ECORRUPT (RMQ_FETCH_VERIFY) */
-  uint32_t reserved;
+  uint32_t reserved;           /* 0, but rmq_fetch_bytes: a request whose first record exceeds its budget
+                                  (status RMQ_ENOSPC) holds that record's size here */
 } rmq_fetch_res;
 
 typedef struct rmq_partition_state {
@@ -386,6 +387,25 @@ int rmq_fetch_async(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32
    what rmq_fetch would have returned (RMQ_OK / RMQ_ENOSPC) with res, out and *bytes_used filled. A
    ticket is answered once; an unknown or already answered ticket gets RMQ_EINVAL. */
 int rmq_fetch_poll(rmq_engine* e, uint64_t ticket, uint32_t wait, uint64_t* bytes_used);
+/* rmq_fetch / rmq_fetch_async with a byte budget per request (FORMAT.md §7 "Byte budgets"; added
+   after ABI 11 without a version bump; a Kafka client's max.partition.fetch.bytes). max_bytes[r] is
+   request r's budget in bytes of record images, 0: none; max_bytes == NULL is exactly rmq_fetch /
+   rmq_fetch_async. A request that would be served more bytes than its budget is answered in every
+   respect as if its max_records had been k*, the largest number of its records whose bytes are at
+   most the budget (count, bytes, later requests' out_pos, the RMQ_ENOSPC test against out_cap,
+   bytes_used, RMQ_FETCH_COMMIT, RMQ_FETCH_VERIFY, RMQ_FETCH_REPLICA). If even its first record
+   exceeds the budget (k* = 0) its row is status RMQ_ENOSPC, count 0, bytes 0, with the first
+   record's size in `reserved` (the budget that would serve it): it takes no output, commits
+   nothing, and the call still returns RMQ_OK (reported per request, as RMQ_ECORRUPT is). A request
+   that does not fit out_cap keeps reserved = 0. Empty slices, RMQ_EOFFSET and error rows are
+   answered as without budgets. With host rows (ordinary or RMQ_FETCH_PINNED_ROWS) max_bytes is
+   ordinary host memory, read before the call returns; with RMQ_FETCH_DEVICE_ROWS it is device
+   memory, 4-byte aligned, valid until the ticket completes. A call with budgets is never held back
+   to go with later asynchronous fetches. rmq_fetch_poll completes both kinds of ticket. */
+int rmq_fetch_bytes(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* max_bytes, uint32_t n,
+                    uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* bytes_used);
+int rmq_fetch_bytes_async(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* max_bytes, uint32_t n,
+                          uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket);
 
 /* ---- replication transport (FORMAT.md §9) ---- */
 /* 128-byte communicator id: one rank creates it, the application hands it to every rank. */

@@ -590,8 +590,9 @@ void free_engine(rmq_engine* e) {
   repair_remote_free(e);
   if (e->state_stage) hipHostFree(e->state_stage);
   for (rmq_engine::FetchSlot& f : e->fslot) {
-    void* fs[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_out};
+    void* fs[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_out, f.d_bud};
     for (void* p : fs) bufs.push_back(p);
+    if (f.h_bud) hipHostFree(f.h_bud);
     if (f.h_req) hipHostFree(f.h_req);
     if (f.h_res) hipHostFree(f.h_res);
     if (f.ev) hipEventDestroy(f.ev);
@@ -1619,12 +1620,13 @@ int fetch_alloc(void** p, size_t bytes) {
 
 int fetch_slot_reserve(rmq_engine::FetchSlot& f, uint32_t n, uint64_t stage, hipStream_t s) {
   if (n > f.cap) {
-    void* ds[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum};
+    void* ds[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_bud};
     for (void* p : ds)
       if (p) hipFree(p);
     if (f.h_req) hipHostFree(f.h_req);
     if (f.h_res) hipHostFree(f.h_res);
-    f.d_req = f.d_cpre = f.h_req = nullptr;
+    if (f.h_bud) hipHostFree(f.h_bud);
+    f.d_req = f.d_cpre = f.h_req = f.h_bud = f.d_bud = nullptr;
     f.d_res = f.d_aux = f.d_csum = f.h_res = nullptr;
     f.cap = 0;
     const uint32_t cap = std::max<uint32_t>(n, 1024);
@@ -1634,6 +1636,7 @@ int fetch_slot_reserve(rmq_engine::FetchSlot& f, uint32_t n, uint64_t stage, hip
     if (!rc) rc = fetch_alloc((void**)&f.d_cpre, ((size_t)cap + 4) * 4);
     const uint32_t lines = cap / kFetchChunk + 2;
     if (!rc) rc = fetch_alloc((void**)&f.d_csum, 2ull * lines * kCsumStride * 8);
+    if (!rc) rc = fetch_alloc((void**)&f.d_bud, (size_t)cap * 4);
     if (rc) return rc;
     // both halves start zeroed (stream-ordered before the slot's first fetch)
     HIP_TRY(hipMemsetAsync(f.d_csum, 0, 2ull * lines * kCsumStride * 8, s));
@@ -1641,6 +1644,7 @@ int fetch_slot_reserve(rmq_engine::FetchSlot& f, uint32_t n, uint64_t stage, hip
     f.csum_par = 0;
     HIP_TRY(hipHostMalloc((void**)&f.h_req, (size_t)cap * 16, 0));
     HIP_TRY(hipHostMalloc((void**)&f.h_res, ((size_t)cap * 4 + 2) * 8, 0));  // res, bytes needed
+    HIP_TRY(hipHostMalloc((void**)&f.h_bud, (size_t)cap * 4, 0));
     f.cap = cap;
   }
   if (stage > f.out_alloc) {
@@ -1720,13 +1724,15 @@ int fetch_slot_step(rmq_engine* e, rmq_engine::FetchSlot& f, bool wait, uint64_t
 
 namespace {
 // Issue a fetch into the next slot: its kernels on the pipeline stream, an event after them.
-int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t mem, uint8_t* out,
-                uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket, bool sync) {
+// max_bytes: the requests' byte budgets (rmq_fetch_bytes, FORMAT.md §7), or null: none.
+int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* max_bytes, uint32_t n, uint32_t mem,
+                uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket, bool sync) {
   if (!e || !ticket) return RMQ_EINVAL;
   bool rows_pinned = (mem & RMQ_FETCH_PINNED_ROWS) != 0;
   const bool rows_dev = (mem & RMQ_FETCH_DEVICE_ROWS) != 0;
   mem &= ~(RMQ_FETCH_PINNED_ROWS | RMQ_FETCH_DEVICE_ROWS);
   if (rows_dev && (rows_pinned || mem != RMQ_MEM_DEVICE)) return RMQ_EINVAL;  // (output on the device too)
+  if (rows_dev && (reinterpret_cast<uintptr_t>(max_bytes) & 3u)) return RMQ_EINVAL;
   if ((n && (!reqs || !res)) || (mem != RMQ_MEM_HOST && mem != RMQ_MEM_DEVICE)) return RMQ_EINVAL;
   if (out_cap && !out) return RMQ_EINVAL;
   if (mem == RMQ_MEM_DEVICE && (reinterpret_cast<uintptr_t>(out) & 15u)) return RMQ_EINVAL;
@@ -1820,6 +1826,22 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t m
   const bool dma = !rows_dev && (e->fetch_dma >= 2 || (e->fetch_dma == 1 && !sync));
   void* h_rs = rows_pinned ? static_cast<void*>(res) : static_cast<void*>(f.h_res);  // (DMA) result rows' host copy
   const bool dma_in = dma && e->fetch_dma_in;
+  // Byte budgets. Host rows: copied now into the slot's page-locked words (the caller's array is
+  // its own again when the call returns), which the trim kernel reads in place, or which go to the
+  // device with the request rows (RMQ_FETCH_DMA); budgets that are all zero are no budgets.
+  // Device rows: read where they are.
+  const uint32_t* d_bud = nullptr;
+  if (max_bytes && rows_dev) {
+    d_bud = max_bytes;
+  } else if (max_bytes) {
+    uint32_t some = 0;
+    for (uint32_t r = 0; r < n; ++r) some |= (f.h_bud[r] = max_bytes[r]);
+    if (some) d_bud = f.h_bud;
+    if (some && dma_in) {
+      HIP_TRY(hipMemcpyAsync(f.d_bud, f.h_bud, (size_t)n * 4, hipMemcpyHostToDevice, e->copy_s));
+      d_bud = f.d_bud;
+    }
+  }
   if (dma_in) {
     HIP_TRY(hipMemcpyAsync(f.d_req, rows_pinned ? static_cast<const void*>(reqs) : static_cast<const void*>(f.h_req),
                            (size_t)n * sizeof(rmq_fetch_req), hipMemcpyHostToDevice, e->copy_s));
@@ -1836,7 +1858,8 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t m
     // tickets in one resolve + gather pair: the requests of different tickets never depend on one
     // another); anything else launches the held ones first, then itself
     // (nor does one with an RMQ_FETCH_VERIFY request: its third kernel follows its own gather)
-    const bool hold = !sync && !any && !verify && !dma && !e->profile && e->fetch_coalesce > 1;
+    // (nor one with byte budgets: its trim kernel runs between its own resolve and gather)
+    const bool hold = !sync && !any && !verify && !d_bud && !dma && !e->profile && e->fetch_coalesce > 1;
     if (!hold) {
       rc = fetch_flush(e);
       if (rc) return rc;
@@ -1879,10 +1902,11 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t m
     // (profiling replays a fetch's kernels back to back; a committing fetch runs once: each run
     // would commit again and the next would read from the committed offset)
     // (nor is a verifying one replayed: its third kernel rewrites the rows the gather wrote)
-    const uint32_t runs = hold ? 0u : e->profile && !any && !verify ? e->fetch_replay : 1u;
+    // (nor a budgeted one: its three kernels are launched without dispatch spans)
+    const uint32_t runs = hold ? 0u : e->profile && !any && !verify && !d_bud ? e->fetch_replay : 1u;
     // (a committing fetch records no dispatch spans: the events the kernels' own dispatches record
     // were measured to hold the second kernel ~10 us behind the first, which its one run would carry)
-    const bool spans = e->profile && !any && !verify;
+    const bool spans = e->profile && !any && !verify && !d_bud;
     if (e->profile) {  // kernel 3: the first run's dispatch spans; 4: every run
       if (spans) {
         for (hipEvent_t& x : ev) x = pool_event(e);
@@ -1899,7 +1923,20 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t m
       a.csum = f.d_csum + half * f.csum_par;
       a.csum_next = f.d_csum + half * (f.csum_par ^ 1u);
       f.csum_par ^= 1u;
-      launch_fetch(a, e->main_s, spans && k == 0 ? ev : nullptr);
+      if (d_bud) {  // resolve, trim, gather
+        FetchTrimArgs t{};
+        t.st = e->st;
+        t.budget = d_bud;
+        t.req_dev = f.d_req;
+        t.res = f.d_res;
+        t.aux = f.d_aux;
+        t.cpre = f.d_cpre;
+        t.csum = a.csum;
+        t.n = n;
+        launch_fetch_budget(a, t, e->main_s);
+      } else {
+        launch_fetch(a, e->main_s, spans && k == 0 ? ev : nullptr);
+      }
       HIP_TRY(hipGetLastError());
     }
     if (verify) {  // the flagged slices checked in the output, then the ticket's commits
@@ -1946,7 +1983,12 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t m
 
 int rmq_fetch_async(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t mem, uint8_t* out,
                     uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket) {
-  return fetch_issue(e, reqs, n, mem, out, out_cap, res, ticket, false);
+  return fetch_issue(e, reqs, nullptr, n, mem, out, out_cap, res, ticket, false);
+}
+
+int rmq_fetch_bytes_async(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* max_bytes, uint32_t n,
+                          uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket) {
+  return fetch_issue(e, reqs, max_bytes, n, mem, out, out_cap, res, ticket, false);
 }
 
 int rmq_fetch_poll(rmq_engine* e, uint64_t ticket, uint32_t wait, uint64_t* bytes_used) {
@@ -1974,7 +2016,18 @@ int rmq_fetch(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t mem
   if (!e) return RMQ_EINVAL;
   if (!n) return RMQ_OK;
   uint64_t t = 0;
-  const int rc = fetch_issue(e, reqs, n, mem, out, out_cap, res, &t, true);
+  const int rc = fetch_issue(e, reqs, nullptr, n, mem, out, out_cap, res, &t, true);
+  if (rc) return rc;
+  return rmq_fetch_poll(e, t, 1, bytes_used);
+}
+
+int rmq_fetch_bytes(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* max_bytes, uint32_t n,
+                    uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* bytes_used) {
+  if (bytes_used) *bytes_used = 0;
+  if (!e) return RMQ_EINVAL;
+  if (!n) return RMQ_OK;
+  uint64_t t = 0;
+  const int rc = fetch_issue(e, reqs, max_bytes, n, mem, out, out_cap, res, &t, true);
   if (rc) return rc;
   return rmq_fetch_poll(e, t, 1, bytes_used);
 }

@@ -20,6 +20,11 @@
 //          (FORMAT.md §1), so no piece straddles a record, the ring end or an output boundary.
 //          (Round 2 placed with a single 1024-thread workgroup between the two: 12.6 us of the
 //          max = 10 fetch of 16,384 requests with the rest of the GPU idle.)
+//  trim    (only a ticket with byte budgets, rmq_fetch_bytes; between the two; a quarter-wave per
+//          request): a served request whose bytes exceed its budget is cut at the last record
+//          start inside the budget, found from the position-keyed sparse index and a walk of the
+//          length words up to the limit, and the words the gather places and copies from are
+//          rewritten.
 //
 // The kernels (resolve, gather; the chunk sums a slot's previous gather cleared) run on the
 // pipeline stream itself, after the last pipeline launch the host had issued and before the next
@@ -480,6 +485,143 @@ __global__ __launch_bounds__(64 * kFW) void fetch_gather_kernel(FetchKArgs<kMult
 }
 
 // ---------------------------------------------------------------------------------------------
+// Byte budgets (rmq_fetch_bytes, FORMAT.md §7): the kernel between the resolve and the gather of a
+// ticket that passes budgets
+// ---------------------------------------------------------------------------------------------
+constexpr u32 kTT = 256;       // threads per trim workgroup
+constexpr u32 kTQ = 64 / kQL;  // requests per trim wave: a quarter-wave each
+
+// load_window's pieces, but only those at or before `limit` (the others read as empty records: the
+// walk never consults them).
+__device__ __forceinline__ WinWords load_window_to(const uint8_t* ring, u64 wb, u32 hl, u64 mask, u64 limit) {
+  WinWords x{};
+#pragma unroll
+  for (u32 k = 0; k < kPPL; ++k) {
+    const u64 p = wb + 16ull * (kPPL * hl + k);
+    if (p <= limit) x.w[k] = *reinterpret_cast<const u32*>(ring + ((p + 8ull) & mask));
+  }
+  return x;
+}
+
+// A quarter-wave per request (16,384 requests: 4,096 waves, one round of the resident waves). A
+// request served RMQ_OK with records whose bytes exceed its budget b is cut at X, the largest
+// record start in [pos0, limit], limit = pos0 + (b & ~15): records and positions are 16-byte
+// aligned, so the records before X are exactly the k* whose bytes are at most b. The sparse index
+// is keyed by position (E[m] = first record start at or after m I, rising with m): the largest m of
+// [ceil(pos0 / I), floor(limit / I)] with E[m].pos <= limit is searched from the top, 16 probes a
+// round (the first round the 16 highest entries: it ends the search unless a record spans 16
+// intervals or more; then 16-ary over what is left below), and from that entry (or from the slice
+// start) the length words up to the limit are read as header windows and walked in registers.
+// Trust, as the resolve's: an entry starts the walk only if it is 16-byte aligned, lies in
+// [pos0, limit] and its offset inside the slice (and it names the slice's first record iff it
+// names its position); the walk reads length words at positions in [pos0, limit] only, every
+// address masked into the ring, stops at the first record that ends past the limit and never
+// counts the slice's last record, so a damaged length word cuts early and is never followed out
+// of the slice.
+__global__ __launch_bounds__(kTT) void fetch_trim_kernel(FetchTrimArgs a) {
+  const DevState& st = a.st;
+  const u32 lane = lane_id(), q = lane / kQL, hl = lane % kQL;
+  const u32 r0 = (blockIdx.x * (kTT / 64) + (threadIdx.x >> 6)) * kTQ;  // the wave's first request
+  const u32 r = r0 + q;
+  const bool live = r < a.n;
+  // one read of the request's words (the same address in the 16 lanes of a quarter)
+  const u32 b = live ? a.budget[r] : 0u;
+  const u64 w2 = live ? a.res[4ull * r + 2] : 0ull, w3 = live ? a.res[4ull * r + 3] : 0ull;
+  const u64 count = (u32)w2, bytes = w2 >> 32;
+  const bool act = live && b != 0u && (int)(u32)w3 == kOk && count > 0 && bytes > (u64)b;
+  if (!__any(act)) return;
+  const u64 off = act ? a.res[4ull * r] : 0ull;
+  const u64 pos0 = act ? a.aux[2ull * r] : 0ull, rw = act ? a.aux[2ull * r + 1] : 0ull;
+  const u32 p = act ? a.req_dev[4ull * r] : 0u, c = act ? a.req_dev[4ull * r + 1] : 0u;  // (served: in range)
+  const u32 ilog = st.interval_log2;
+  const RingRef rg = ring_ref(act ? st.ring[p] : 0ull, ilog, st.icap_mul);
+  const uint8_t* ring = st.logs + (rw >> 6);
+  const u64 mask = (1ull << (rw & 63ull)) - 1ull;
+  const u64* E = st.index + rg.ibase * 2;
+  const u64 limit = pos0 + (u64)(b & ~15u);
+  constexpr u32 kQMask = (1u << kQL) - 1u;
+  // the index entry to start from (quarter-uniform state)
+  u64 c_off = off, c_pos = pos0;
+  long lo = (long)((pos0 + (1ull << ilog) - 1ull) >> ilog), hi = (long)(limit >> ilog), step = 1;
+  bool open = act && lo <= hi;
+  while (__any(open)) {
+    const long m = hi - (long)hl * step;  // probes from the top of the range
+    bool ok = false;
+    u64 eo = 0, ep = 0;
+    if (open && m >= lo) {
+      const u64* e = E + ((u64)m % rg.icap) * 2;
+      eo = e[0];
+      ep = e[1];
+      ok = !(ep & 15ull) && ep >= pos0 && ep <= limit && eo >= off && eo < off + count && ((eo == off) == (ep == pos0));
+    }
+    const u32 bal = (u32)(__ballot(ok) >> (kQL * q)) & kQMask;  // this quarter's probes
+    const u32 top = bal ? (u32)__builtin_ctz(bal) : 0u;          // the highest entry at or before the limit
+    const u64 so = shfl_u64(eo, (int)(kQL * q + top)), sp = shfl_u64(ep, (int)(kQL * q + top));
+    if (open) {
+      if (!bal) {  // every probe past the limit: the answer lies below this round's lowest probe
+        hi -= (long)(kQL - 1) * step + 1;
+      } else {
+        c_off = so;
+        c_pos = sp;
+        const long mk = hi - (long)top * step;
+        lo = mk + 1;  // that probe, or an entry between it and the probe above it
+        hi = step == 1 ? mk : min(hi, mk + step - 1);
+      }
+      open = lo <= hi;
+      step = (hi - lo + (long)kQL) / (long)kQL;
+    }
+  }
+  // the walk: records from c_pos while they end at or before the limit
+  constexpr u32 kWin = kPPL * kQL;  // pieces per header window
+  u64 wb = c_pos, cur = 0, k = c_off - off, rs_last = 0;
+  WinWords Lw{};
+  if (act) Lw = load_window_to(ring, wb, hl, mask, limit);
+  bool go = act;
+  while (__any(go)) {
+    const bool mv = go && cur >= kWin;  // quarter-uniform: the quarter walked off its window
+    if (__any(mv)) {
+      if (mv) {
+        wb += 16ull * cur;
+        cur = 0;
+        Lw = load_window_to(ring, wb, hl, mask, limit);
+      }
+    }
+    const u32 src = kQL * q + ((u32)cur / kPPL);
+    u32 len = 0;
+#pragma unroll
+    for (u32 j = 0; j < kPPL; ++j) {
+      const u32 x = (u32)__shfl((int)Lw.w[j], (int)(src & 63u), 64);
+      len = ((u32)cur % kPPL) == j ? x : len;
+    }
+    if (go) {
+      const u64 rs = 16ull + (((u64)len + 15ull) & ~15ull);
+      if (wb + 16ull * cur + rs <= limit && k + 1 < count) {
+        cur += rs >> 4;
+        ++k;
+      } else {
+        go = false;
+        rs_last = rs;
+      }
+    }
+  }
+  const u64 nb = k ? wb + 16ull * cur - pos0 : 0ull;  // the trimmed slice's bytes
+  if (act && hl == 0) {
+    a.res[4ull * r + 2] = k | (nb << 32);
+    // no record fits: RMQ_ENOSPC for this request alone, the first record's size in `reserved`
+    if (!k) a.res[4ull * r + 3] = (u64)(uint32_t)kNoSpc | ((rs_last < bytes ? rs_last : bytes) << 32);
+    a.cpre[r] = (u32)nb;
+    *reinterpret_cast<ulonglong2*>(st.pcache + ((u64)p * st.C + c) * 2) = make_ulonglong2(off + k, pos0 + nb);
+  }
+  // the bytes removed leave the chunk's sum: one subtract per wave (its requests share a chunk)
+  static_assert(kFetchChunk % kTQ == 0, "a trim wave never straddles a chunk");
+  u64 cut = act ? bytes - nb : 0ull, cut_w = 0;
+#pragma unroll
+  for (u32 j = 0; j < kTQ; ++j) cut_w += bcast_u64(cut, kQL * j);
+  if (lane == 0 && cut_w)
+    atomicAdd((unsigned long long*)&a.csum[(u64)(r0 / kFetchChunk) * kCsumStride], (unsigned long long)(0ull - cut_w));
+}
+
+// ---------------------------------------------------------------------------------------------
 // RMQ_FETCH_VERIFY (FORMAT.md §10): the third kernel of a ticket with a flagged request
 // ---------------------------------------------------------------------------------------------
 constexpr int kCorrupt = -10;
@@ -635,6 +777,7 @@ void preload_fetch_kernels() {
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_gather_kernel<false>));
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_resolve_kernel<true>));
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_gather_kernel<true>));
+  (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_trim_kernel));
 }
 
 static void launch_batch(const FetchBatch& b, hipStream_t s, const hipEvent_t* e) {
@@ -661,6 +804,13 @@ void launch_fetch_batch(const FetchArgs* t, uint32_t nt, hipStream_t s) {
     b.gwg0[k + 1] = b.gwg0[k] + (t[k].n + kGR - 1) / kGR;
   }
   launch_batch(b, s, nullptr);
+}
+
+void launch_fetch_budget(const FetchArgs& a, const FetchTrimArgs& t, hipStream_t s) {
+  if (!a.n) return;
+  hipLaunchKernelGGL(fetch_resolve_kernel<false>, dim3((a.n + kRW * kRPW - 1) / (kRW * kRPW)), dim3(64 * kRW), 0, s, a);
+  hipLaunchKernelGGL(fetch_trim_kernel, dim3((a.n + (kTT / 64) * kTQ - 1) / ((kTT / 64) * kTQ)), dim3(kTT), 0, s, t);
+  hipLaunchKernelGGL(fetch_gather_kernel<false>, dim3((a.n + kGR - 1) / kGR), dim3(64 * kFW), 0, s, a);
 }
 
 void launch_fetch(const FetchArgs& a, hipStream_t s, const hipEvent_t* ev) {

@@ -352,6 +352,21 @@ struct FetchVerifyArgs {
   uint32_t pad;
 };
 constexpr uint32_t kCsumStride = 16;   // u64 words per chunk sum (128 bytes)
+// The kernel between the resolve and the gather of a ticket with byte budgets (rmq_fetch_bytes,
+// FORMAT.md §7 "Byte budgets"; its own arguments, as the verify kernel's): it cuts every served
+// request whose bytes exceed its budget at a record boundary and rewrites the words the gather
+// places and copies from (the resolve's row words, cpre, the chunk sum, the position cache entry).
+struct FetchTrimArgs {
+  DevState st;
+  const uint32_t* budget;    // [n] bytes per request, 0: none (page-locked host or device memory)
+  const uint32_t* req_dev;   // [n][4] the resolve's device copy of the request rows
+  uint64_t* res;             // [n][4] the resolve's row words (FetchArgs::res)
+  const uint64_t* aux;       // [n][2] {source byte position, ring word} (FetchArgs::aux)
+  uint32_t* cpre;            // [n] bytes of each request (FetchArgs::cpre)
+  uint64_t* csum;            // the ticket's chunk sums (FetchArgs::csum)
+  uint32_t n;
+  uint32_t pad;
+};
 
 
 
@@ -576,6 +591,8 @@ void launch_late_retention(const LateArgs& a, hipStream_t s);
 void launch_become_leader(const DevState& st, uint32_t pidx, hipStream_t s);
 void launch_fetch(const FetchArgs& a, hipStream_t s, const hipEvent_t* ev4);
 void launch_fetch_batch(const FetchArgs* t, uint32_t nt, hipStream_t s);  // nt <= kFetchBatch tickets, one pair
+// One ticket with byte budgets: resolve, trim, gather (t's res, aux, cpre, csum are a's).
+void launch_fetch_budget(const FetchArgs& a, const FetchTrimArgs& t, hipStream_t s);
 void launch_fetch_verify(const FetchVerifyArgs& a, uint32_t max_wgs, hipStream_t s);  // after the ticket's gather
 void preload_fetch_kernels();
 

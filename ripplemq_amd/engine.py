@@ -35,6 +35,17 @@ _PTRS: dict = {}  # id(array) -> (weak reference, data address): arrays a caller
 _PTR_CACHE = os.environ.get("RMQ_PY_PTR_CACHE", "1") != "0"  # (A/B of the cache)
 
 
+def _budgets(max_bytes, n: int) -> np.ndarray | None:
+    """The byte budgets of n fetch requests as rmq_fetch_bytes takes them: an array, or a scalar for
+    every request; None: no budgets (plain rmq_fetch)."""
+    if max_bytes is None:
+        return None
+    b = np.broadcast_to(np.asarray(max_bytes, np.uint64), (n,))
+    if np.any(b > 0xFFFFFFFF):
+        raise ValueError("max_bytes: budgets are 32-bit")
+    return np.ascontiguousarray(b, np.uint32)
+
+
 def _ptr_reused(a: np.ndarray) -> int:
     """_ptr of an array passed again and again (a fetch's request and result rows, views of
     page-locked memory from fetch_rows): numpy's .ctypes.data costs ~1.5 us a call, a checked cache
@@ -399,14 +410,22 @@ class Engine:
         return rc
 
     def fetch(self, pidx, consumer, max_records, out_cap: int | None = None, commit: bool = False,
-              out: np.ndarray | None = None, replica: bool = False, verify: bool = False):
+              out: np.ndarray | None = None, replica: bool = False, verify: bool = False, max_bytes=None):
         """rmq_fetch into a host array (sized by a first call when out_cap is None, or the caller's
         uint8 `out`, e.g. page-locked from host_empty: one call, RMQ_ENOSPC if it is too small);
         commit: RMQ_FETCH_COMMIT on every request (the size query commits nothing); replica:
         RMQ_FETCH_REPLICA (this engine's own replica from its replica cursor, leader or follower);
         verify: RMQ_FETCH_VERIFY (a slice with a record that fails its checks comes back
-        RMQ_ECORRUPT with count 0)."""
+        RMQ_ECORRUPT with count 0). max_bytes: a byte budget per request (an array, or one value
+        for all; 0: none): rmq_fetch_bytes, FORMAT.md §7."""
         n = len(pidx)
+        bud = _budgets(max_bytes, n)
+
+        def call(*a):  # rmq_fetch, or rmq_fetch_bytes with the budgets after the requests
+            if bud is None:
+                return self.lib.rmq_fetch(*a)
+            return self.lib.rmq_fetch_bytes(a[0], a[1], _ptr(bud), *a[2:])
+
         req = np.zeros((n, 4), np.uint32)
         req[:, 0], req[:, 1], req[:, 2] = pidx, consumer, max_records
         req[:, 3] = (A.RMQ_FETCH_REPLICA if replica else 0) | (A.RMQ_FETCH_VERIFY if verify else 0)
@@ -415,14 +434,13 @@ class Engine:
             if commit:
                 req[:, 3] |= A.RMQ_FETCH_COMMIT
             used = C.c_uint64()
-            rc = self.lib.rmq_fetch(self.h, _ptr(req), n, A.RMQ_MEM_HOST, _ptr(out), out.size, _ptr(res),
-                                    C.byref(used))
+            rc = call(self.h, _ptr(req), n, A.RMQ_MEM_HOST, _ptr(out), out.size, _ptr(res), C.byref(used))
             if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
                 raise EngineError(rc, "rmq_fetch")
             return rc, res, out, int(used.value)
         if out_cap is None:
             used = C.c_uint64()
-            rc = self.lib.rmq_fetch(self.h, _ptr(req), n, A.RMQ_MEM_HOST, None, 0, _ptr(res), C.byref(used))
+            rc = call(self.h, _ptr(req), n, A.RMQ_MEM_HOST, None, 0, _ptr(res), C.byref(used))
             if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
                 raise EngineError(rc, "rmq_fetch")
             out_cap = int(used.value)
@@ -430,25 +448,34 @@ class Engine:
             req[:, 3] |= A.RMQ_FETCH_COMMIT
         out = np.zeros(max(out_cap, 1), np.uint8)
         used = C.c_uint64()
-        rc = self.lib.rmq_fetch(self.h, _ptr(req), n, A.RMQ_MEM_HOST, _ptr(out), out_cap, _ptr(res), C.byref(used))
+        rc = call(self.h, _ptr(req), n, A.RMQ_MEM_HOST, _ptr(out), out_cap, _ptr(res), C.byref(used))
         if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
             raise EngineError(rc, "rmq_fetch")
         return rc, res, out[:out_cap], int(used.value)
 
     def fetch_device(self, pidx, consumer, max_records, d_out: int, out_cap: int, commit: bool = False,
                      req: np.ndarray | None = None, res: np.ndarray | None = None, pinned_rows: bool = False,
-                     d_rows: tuple[int, int, int] | None = None, verify: bool = False):
+                     d_rows: tuple | None = None, verify: bool = False, max_bytes=None):
         """rmq_fetch into a device buffer (16-byte aligned); returns (rc, res, bytes_used). req / res:
         the caller's arrays (pidx / consumer / max_records None leave req's columns as they are);
         pinned_rows: page-locked ones (fetch_rows), read and written by the kernels in place
         (RMQ_FETCH_PINNED_ROWS). d_rows = (n, device request rows, device result rows): rows in
-        device memory (RMQ_FETCH_DEVICE_ROWS, flags ignored); res is then None. verify:
-        RMQ_FETCH_VERIFY on every request (host rows only)."""
+        device memory (RMQ_FETCH_DEVICE_ROWS, flags ignored), with an optional fourth element, the
+        device array of the requests' byte budgets (uint32[n]); res is then None. verify:
+        RMQ_FETCH_VERIFY on every request (host rows only). max_bytes: byte budgets of host rows, as
+        for fetch."""
         if d_rows is not None:
-            n, d_req, d_res = d_rows
+            n, d_req, d_res = d_rows[:3]
+            if max_bytes is not None:
+                raise ValueError("device rows take their budgets as d_rows' fourth element")
             used = C.c_uint64()
-            rc = self.lib.rmq_fetch(self.h, C.c_void_p(d_req), n, A.RMQ_MEM_DEVICE | A.RMQ_FETCH_DEVICE_ROWS,
-                                    d_out, out_cap, C.c_void_p(d_res), C.byref(used))
+            mem = A.RMQ_MEM_DEVICE | A.RMQ_FETCH_DEVICE_ROWS
+            if len(d_rows) > 3 and d_rows[3]:
+                rc = self.lib.rmq_fetch_bytes(self.h, C.c_void_p(d_req), C.c_void_p(d_rows[3]), n, mem,
+                                              d_out, out_cap, C.c_void_p(d_res), C.byref(used))
+            else:
+                rc = self.lib.rmq_fetch(self.h, C.c_void_p(d_req), n, mem, d_out, out_cap, C.c_void_p(d_res),
+                                        C.byref(used))
             if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
                 raise EngineError(rc, "rmq_fetch")
             return rc, None, int(used.value)
@@ -465,7 +492,12 @@ class Engine:
             res = np.zeros(n, FETCH_RES_DTYPE)
         used = C.c_uint64()
         mem = A.RMQ_MEM_DEVICE | (A.RMQ_FETCH_PINNED_ROWS if pinned_rows else 0)
-        rc = self.lib.rmq_fetch(self.h, _ptr_reused(req), n, mem, d_out, out_cap, _ptr_reused(res), C.byref(used))
+        bud = _budgets(max_bytes, n)
+        if bud is None:
+            rc = self.lib.rmq_fetch(self.h, _ptr_reused(req), n, mem, d_out, out_cap, _ptr_reused(res), C.byref(used))
+        else:
+            rc = self.lib.rmq_fetch_bytes(self.h, _ptr_reused(req), _ptr(bud), n, mem, d_out, out_cap,
+                                          _ptr_reused(res), C.byref(used))
         if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
             raise EngineError(rc, "rmq_fetch")
         return rc, res, int(used.value)
@@ -473,7 +505,7 @@ class Engine:
     def fetch_async(self, pidx, consumer, max_records, d_out: int | None = None, out_cap: int = 0,
                     out: np.ndarray | None = None, req: np.ndarray | None = None,
                     res: np.ndarray | None = None, pinned_rows: bool = False,
-                    verify: bool = False) -> "FetchTicket":
+                    verify: bool = False, max_bytes=None) -> "FetchTicket":
         """rmq_fetch_async into a device buffer (d_out, 16-byte aligned) or a host array (out): the
         call returns at once; fetch_poll(ticket) gives (rc, res, bytes_used) once it completes. The
         handle keeps the request, result and output arrays alive until then. req ([n, 4] uint32)
@@ -481,7 +513,8 @@ class Engine:
         given, pidx / consumer / max_records None leave those columns as they are (column 3: the
         requests' flags, RMQ_FETCH_COMMIT). pinned_rows: req and res are page-locked (fetch_rows)
         and the kernels read and write them in place (RMQ_FETCH_PINNED_ROWS); req then stays
-        unchanged until the ticket completes. verify: RMQ_FETCH_VERIFY ORed into every request."""
+        unchanged until the ticket completes. verify: RMQ_FETCH_VERIFY ORed into every request.
+        max_bytes: byte budgets, as for fetch (rmq_fetch_bytes_async; read before the call returns)."""
         n = len(pidx) if pidx is not None else len(req)
         if pinned_rows and (req is None or res is None):
             raise ValueError("pinned_rows needs the caller's page-locked req and res (fetch_rows)")
@@ -503,8 +536,13 @@ class Engine:
         if pinned_rows:
             mem |= A.RMQ_FETCH_PINNED_ROWS
         t = C.c_uint64()
-        _check(self.lib.rmq_fetch_async(self.h, _ptr_reused(req), n, mem, ptr, out_cap, _ptr_reused(res), C.byref(t)),
-               "rmq_fetch_async")
+        bud = _budgets(max_bytes, n)
+        if bud is None:
+            _check(self.lib.rmq_fetch_async(self.h, _ptr_reused(req), n, mem, ptr, out_cap, _ptr_reused(res), C.byref(t)),
+                   "rmq_fetch_async")
+        else:
+            _check(self.lib.rmq_fetch_bytes_async(self.h, _ptr_reused(req), _ptr(bud), n, mem, ptr, out_cap,
+                                                  _ptr_reused(res), C.byref(t)), "rmq_fetch_bytes_async")
         tk = FetchTicket(t.value, req, res, out)
         self._fetching[t.value] = tk
         return tk

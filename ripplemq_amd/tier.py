@@ -15,7 +15,10 @@ The engine's replica rings keep a retained window only (FORMAT.md §4): a fetch 
   persists its replica too, so a leader moved to it serves consumers below its rings from its own
   files. A segment file holds the records exactly as the rings do (FORMAT.md
   §1: 16-byte header {offset, length, CRC32C} + payload padded to 16 bytes), named by its first
-  offset (``p<pidx>/<first offset>.seg``), rolled at ``segment_file_bytes``.
+  offset (``p<pidx>/<first offset>.seg``), rolled at ``segment_file_bytes``. With
+  ``DurableLog(spill_bytes=N)`` the spill keeps one buffer of ``N`` bytes and reads in passes of
+  byte-budgeted fetches (``rmq_fetch_bytes``) instead of growing a buffer to whatever the
+  partitions hold.
 * ``DurableLog.read(p, off, max)`` serves ``[off, min(off + max, durable end))`` from the files
   (the broker's ``process_batch_read`` falls back to it on ``RMQ_EOFFSET`` after a spill, so a
   consumer below the rings gets what the reference's list would give it).
@@ -40,6 +43,7 @@ records were lost before they were durable.
 from __future__ import annotations
 
 import ctypes as C
+import inspect
 import json
 import os
 import time
@@ -305,7 +309,14 @@ class DurableLog:
     replica of, led or followed), fed by spill from the engine's own replica."""
 
     def __init__(self, engine, directory: str, partitions, cursor: int, *,
-                 segment_file_bytes: int = 64 << 20, fsync: bool = False, start=None):
+                 segment_file_bytes: int = 64 << 20, fsync: bool = False, start=None,
+                 spill_bytes: int | None = None):
+        # spill_bytes: spill through one buffer of at most that many bytes, never grown, in passes of
+        # byte-budgeted fetches (rmq_fetch_bytes); None: one fetch into a buffer grown to fit
+        self.spill_bytes = None if spill_bytes is None else int(spill_bytes) & ~15
+        if spill_bytes is not None:
+            if "max_bytes" not in inspect.signature(engine.fetch).parameters:
+                raise ValueError("spill_bytes needs an engine whose fetch takes byte budgets (max_bytes)")
         self.engine = engine
         self.dir = directory
         self.cursor = int(cursor)
@@ -313,6 +324,8 @@ class DurableLog:
         ends = load_ends(directory)
         self.parts = {int(p): _PartitionFiles(directory, int(p), segment_file_bytes, ends.get(int(p), 0))
                       for p in partitions}
+        if self.spill_bytes is not None and self.spill_bytes < 16 * max(len(self.parts), 1):
+            raise ValueError("spill_bytes: at least 16 bytes per partition")
         self._saved = None  # [partition of parts][row, term, voted term, voted for] as last saved
         self._buf = None    # the spill's fetch output (reused)
         # every partition's spill state as arrays (a spill of thousands of partitions runs no
@@ -394,6 +407,8 @@ class DurableLog:
             return 0
         cons = np.full(len(pidx), self.cursor, np.uint32)
         mx = np.full(len(pidx), 0xFFFFFFFF, np.uint32)
+        if self.spill_bytes is not None:
+            return self._spill_bounded(pidx, cons, mx, t0)
         # one fetch into a reused buffer (page-locked when the engine offers it), grown when short
         while True:
             if self._buf is not None:
@@ -412,8 +427,19 @@ class DurableLog:
             else:
                 self._buf = np.zeros(need, np.uint8)
         t1 = time.perf_counter()
+        moved = self._append_runs(pidx, res, buf)
+        t2 = time.perf_counter()
+        self._save_state(pidx, t0, t1, t2)
+        return moved
+
+    def _append_runs(self, pidx, res, buf, budgeted: bool = False) -> int:
+        """The served runs of one spill fetch into their segment files; returns the records written.
+        budgeted: rows answered RMQ_ENOSPC for their byte budget (count 0) are no errors."""
         status = res["status"].astype(np.int64)
-        bad = np.flatnonzero(status != A.RMQ_OK)
+        ok = status == A.RMQ_OK
+        if budgeted:
+            ok |= (status == A.RMQ_ENOSPC) & (res["reserved"] > 0)
+        bad = np.flatnonzero(~ok)
         if len(bad):
             p, st = int(pidx[bad[0]]), int(status[bad[0]])
             raise EngineError(st, f"spill of partition {p} (records lost before they were durable)"
@@ -460,9 +486,53 @@ class DurableLog:
             self._end[sel] += count.astype(np.int64)
             self._total[sel] += nbytes.astype(np.int64)
             moved = int(count.sum())
-            t2 = time.perf_counter()
-        else:
-            t2 = time.perf_counter()
+        return moved
+
+    def _spill_bounded(self, pidx, cons, mx, t0) -> int:
+        """spill through one buffer of spill_bytes, in passes: every partition's budget is an equal
+        16-byte-aligned share of it, so no request ever fails for capacity and no cursor is reset. A
+        partition whose next record exceeds its share (a row answered RMQ_ENOSPC with the record's
+        size in `reserved`) gets that size in the next pass, the others sharing what is left."""
+        n, cap = len(pidx), self.spill_bytes
+        if self._buf is None:
+            self._buf = self.engine.host_empty(cap, np.uint8) if hasattr(self.engine, "host_empty") else np.zeros(cap, np.uint8)
+        want = np.zeros(n, np.int64)  # the record size a partition asked for in the last pass
+        moved, t_fetch, t_files = 0, 0.0, 0.0
+        while True:
+            ta = time.perf_counter()
+            # the asking partitions first, as many as fit; the others share the rest (a partition
+            # left without 16 bytes, or whose record can never fit, sits the pass out: max_records
+            # 0, never a budget of 0)
+            never = want > cap
+            big = np.flatnonzero((want > 0) & ~never)
+            take = big[np.cumsum(want[big]) <= cap]
+            bud = np.zeros(n, np.int64)
+            bud[take] = want[take]
+            rest = np.setdiff1d(np.arange(n), take)
+            if len(rest):
+                bud[rest] = ((cap - int(bud.sum())) // len(rest)) & ~15
+            mxp = np.where((bud >= 16) & ~never, mx, 0).astype(np.uint32)
+            rc, res, buf, used = self.engine.fetch(pidx, cons, mxp, out=self._buf, commit=True, replica=True,
+                                                   max_bytes=np.maximum(bud, 16))
+            if rc != A.RMQ_OK:
+                raise EngineError(rc, "spill: budgeted fetch")
+            tb = time.perf_counter()
+            m = self._append_runs(pidx, res, buf, budgeted=True)
+            t_fetch, t_files = t_fetch + tb - ta, t_files + time.perf_counter() - tb
+            moved += m
+            asked = res["status"] == A.RMQ_ENOSPC
+            want = np.where(asked, res["reserved"].astype(np.int64), np.where(mxp == 0, want, 0))
+            if not m and not ((want > 0) & (want <= cap)).any():
+                break
+        # (what the passes wrote is durable and recorded before a record too large is reported)
+        self._save_state(pidx, t0, t0 + t_fetch, t0 + t_fetch + t_files)
+        if (want > cap).any():
+            k = int(np.flatnonzero(want > cap)[0])
+            raise EngineError(A.RMQ_ENOSPC, f"spill of partition {int(pidx[k])}: a record of {int(want[k])} bytes "
+                                            f"exceeds spill_bytes = {cap}")
+        return moved
+
+    def _save_state(self, pidx, t0, t1, t2) -> None:
         t3 = time.perf_counter()
         # offsets and term of the partitions led here (one bulk read of each), then the durable ends
         # of every partition in one file: a reopen trusts the records below them
@@ -504,7 +574,6 @@ class DurableLog:
         for k, v in (("fetch", t1 - t0), ("files", t2 - t1), ("commit", t3 - t2), ("table", t3a - t3),
                      ("states", t3b - t3a), ("save", t3c - t3b), ("ends", t4 - t3c)):
             self.phase_s[k] = self.phase_s.get(k, 0.0) + v
-        return moved
 
     def read(self, p: int, off: int, max_messages: int) -> list[tuple[int, int, bytes]]:
         """Records [off, min(off + max, durable end)) of partition p from the files."""
