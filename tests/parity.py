@@ -77,13 +77,37 @@ def compare_index_slots(dev, ora, cfg, p):
                              f"gpu={got[bad[:4]].tolist()} want={want[bad[:4]].tolist()}")
 
 
+def pipelined(dev, ora, batches):
+    """Submit every batch before waiting for any (the engine coalesces them into launch groups of
+    cfg.pipeline_depth), then check each batch's offsets and stats against the oracle applying the
+    batches one at a time. Returns the stats of every batch."""
+    subs = [dev.append_async(b.pidx, b.lens, b.payload) for b in batches]
+    stats = []
+    for (t, out), b in zip(subs, batches):
+        sd = dev.wait(t)
+        oo, so = ora.append(b.pidx, b.lens, b.payload)
+        assert sd == so, f"append stats gpu={sd} cpu={so}"
+        if not np.array_equal(out, oo):
+            bad = np.flatnonzero(out != oo)
+            raise AssertionError(f"out_offsets differ at {bad[:8]}: gpu={out[bad[:8]]} cpu={oo[bad[:8]]}")
+        stats.append(sd)
+    return stats
+
+
 def run_ops(dev, ora, cfg, ops, check=True, full_rings=False, parts=None, local_slots=None):
     """Apply ops to both engines, comparing outputs of every op and state after each append."""
     log = []
     submitted = appended = 0
     for op in ops:
         kind = op[0]
-        if kind == "append":
+        if kind == "pipelined":
+            for b, sd in zip(op[1], pipelined(dev, ora, op[1])):
+                log.append(("append", sd))
+                submitted += len(b.pidx)
+                appended += sd["appended"]
+            if check:
+                compare_state(dev, ora, cfg, parts, full_rings, local_slots)
+        elif kind == "append":
             b: Batch = op[1]
             poff = op[2] if len(op) > 2 else None
             payload = op[3] if len(op) > 3 else b.payload

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from parity import compare_state, run_ops
+from parity import pipelined as _pipelined
 from ripplemq_amd.engine import Engine, EngineConfig
 from ripplemq_amd.workload import Batch, StreamSpec, make_batch
 
@@ -257,20 +258,6 @@ def test_read_then_commit_consume_loop(oracle_mod):
                 eng.commit_consumer_offset([0, 1, 2], [0, 0, 0], res["start_offset"] + res["count"])
         compare_state(dev, ora, cfg)
         assert [int(dev.consumer_offsets(p)[0]) for p in range(3)] == [32, 32, 31]
-
-
-def _pipelined(dev, ora, batches):
-    """Submit every batch before waiting for any (the engine coalesces them into launch groups of
-    cfg.pipeline_depth), then check each batch's offsets and stats against the oracle applying the
-    batches one at a time."""
-    subs = [dev.append_async(b.pidx, b.lens, b.payload) for b in batches]
-    for (t, out), b in zip(subs, batches):
-        sd = dev.wait(t)
-        oo, so = ora.append(b.pidx, b.lens, b.payload)
-        assert sd == so, f"append stats gpu={sd} cpu={so}"
-        if not np.array_equal(out, oo):
-            bad = np.flatnonzero(out != oo)
-            raise AssertionError(f"out_offsets differ at {bad[:8]}: gpu={out[bad[:8]]} cpu={oo[bad[:8]]}")
 
 
 @pytest.mark.parametrize("group", [1, 2, 3, 4, 8])
