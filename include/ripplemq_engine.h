@@ -406,6 +406,31 @@ int rmq_fetch_bytes(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* ma
                     uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* bytes_used);
 int rmq_fetch_bytes_async(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* max_bytes, uint32_t n,
                           uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket);
+/* rmq_fetch_bytes / rmq_fetch_bytes_async with an explicit start offset per request (FORMAT.md §7
+   "Explicit offsets"; added after ABI 11 without a version bump; the fetch offset of a Kafka fetch
+   request). offsets[r] == RMQ_OFFSET_NONE: request r is answered as ever, from its consumer's
+   committed offset (or the replica cursor with RMQ_FETCH_REPLICA); any other value is the request's
+   `off` instead, and the request is answered in every respect as if the committed offset (the
+   replica cursor) had been that value when the call was ordered: an offset at or past the high
+   watermark gives an empty RMQ_OK row with start_offset = off, one before the log start
+   RMQ_EOFFSET with the first retained offset; max_records, byte budgets, out_pos, the RMQ_ENOSPC
+   test, bytes_used and RMQ_FETCH_VERIFY as without it. Offset 2^64 - 1 itself cannot be asked for
+   (a slice there is always empty). Nothing is written without RMQ_FETCH_COMMIT: neither the
+   consumer table nor the replica cursor moves, and no round carries anything; with it the request
+   commits start_offset + count (the first retained offset after RMQ_EOFFSET), a seek and a read
+   in one call. A call may hold several non-committing requests of one (partition, consumer), at
+   most one committing one. `consumer` must still be below max_consumers: it keys the position
+   cache, which explicit requests consult and update like any other, and names the row a commit
+   writes. offsets == NULL is exactly rmq_fetch_bytes / rmq_fetch_bytes_async (with max_bytes ==
+   NULL too: rmq_fetch / rmq_fetch_async). With host rows (ordinary or RMQ_FETCH_PINNED_ROWS)
+   offsets is ordinary host memory, read before the call returns; with RMQ_FETCH_DEVICE_ROWS it is
+   device memory, 8-byte aligned (RMQ_EINVAL otherwise), valid until the ticket completes. A call
+   with offsets is never held back to go with later asynchronous fetches. rmq_fetch_poll completes
+   these tickets too. */
+int rmq_fetch_at(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
+                 uint32_t n, uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* bytes_used);
+int rmq_fetch_at_async(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
+                       uint32_t n, uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket);
 
 /* ---- replication transport (FORMAT.md §9) ---- */
 /* 128-byte communicator id: one rank creates it, the application hands it to every rank. */

@@ -590,9 +590,10 @@ void free_engine(rmq_engine* e) {
   repair_remote_free(e);
   if (e->state_stage) hipHostFree(e->state_stage);
   for (rmq_engine::FetchSlot& f : e->fslot) {
-    void* fs[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_out, f.d_bud};
+    void* fs[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_out, f.d_bud, f.d_at};
     for (void* p : fs) bufs.push_back(p);
     if (f.h_bud) hipHostFree(f.h_bud);
+    if (f.h_at) hipHostFree(f.h_at);
     if (f.h_req) hipHostFree(f.h_req);
     if (f.h_res) hipHostFree(f.h_res);
     if (f.ev) hipEventDestroy(f.ev);
@@ -1620,14 +1621,15 @@ int fetch_alloc(void** p, size_t bytes) {
 
 int fetch_slot_reserve(rmq_engine::FetchSlot& f, uint32_t n, uint64_t stage, hipStream_t s) {
   if (n > f.cap) {
-    void* ds[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_bud};
+    void* ds[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_bud, f.d_at};
     for (void* p : ds)
       if (p) hipFree(p);
     if (f.h_req) hipHostFree(f.h_req);
     if (f.h_res) hipHostFree(f.h_res);
     if (f.h_bud) hipHostFree(f.h_bud);
+    if (f.h_at) hipHostFree(f.h_at);
     f.d_req = f.d_cpre = f.h_req = f.h_bud = f.d_bud = nullptr;
-    f.d_res = f.d_aux = f.d_csum = f.h_res = nullptr;
+    f.d_res = f.d_aux = f.d_csum = f.h_res = f.h_at = f.d_at = nullptr;
     f.cap = 0;
     const uint32_t cap = std::max<uint32_t>(n, 1024);
     int rc = fetch_alloc((void**)&f.d_req, (size_t)cap * 16);
@@ -1725,7 +1727,9 @@ int fetch_slot_step(rmq_engine* e, rmq_engine::FetchSlot& f, bool wait, uint64_t
 namespace {
 // Issue a fetch into the next slot: its kernels on the pipeline stream, an event after them.
 // max_bytes: the requests' byte budgets (rmq_fetch_bytes, FORMAT.md §7), or null: none.
-int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* max_bytes, uint32_t n, uint32_t mem,
+// offsets: the requests' explicit offsets (rmq_fetch_at, FORMAT.md §7), or null: none.
+int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
+                uint32_t n, uint32_t mem,
                 uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket, bool sync) {
   if (!e || !ticket) return RMQ_EINVAL;
   bool rows_pinned = (mem & RMQ_FETCH_PINNED_ROWS) != 0;
@@ -1733,6 +1737,7 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* max_by
   mem &= ~(RMQ_FETCH_PINNED_ROWS | RMQ_FETCH_DEVICE_ROWS);
   if (rows_dev && (rows_pinned || mem != RMQ_MEM_DEVICE)) return RMQ_EINVAL;  // (output on the device too)
   if (rows_dev && (reinterpret_cast<uintptr_t>(max_bytes) & 3u)) return RMQ_EINVAL;
+  if (rows_dev && (reinterpret_cast<uintptr_t>(offsets) & 7u)) return RMQ_EINVAL;
   if ((n && (!reqs || !res)) || (mem != RMQ_MEM_HOST && mem != RMQ_MEM_DEVICE)) return RMQ_EINVAL;
   if (out_cap && !out) return RMQ_EINVAL;
   if (mem == RMQ_MEM_DEVICE && (reinterpret_cast<uintptr_t>(out) & 15u)) return RMQ_EINVAL;
@@ -1842,6 +1847,28 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* max_by
       d_bud = f.d_bud;
     }
   }
+  // Explicit offsets, as the budgets. Host rows: copied now into the slot's page-locked words, which
+  // the resolve reads in place (or which go to the device with the request rows); offsets that are
+  // all RMQ_OFFSET_NONE are no offsets. Device rows: read where they are.
+  const uint64_t* d_at = nullptr;
+  if (offsets && rows_dev) {
+    d_at = offsets;
+  } else if (offsets) {
+    // (the slot's offset words are made by its first call that passes offsets: a slot that never
+    // sees one holds the scratch it always held; fetch_slot_reserve frees them when the slot grows)
+    if (!f.h_at) HIP_TRY(hipHostMalloc((void**)&f.h_at, (size_t)f.cap * 8, 0));
+    if (!f.d_at && dma_in) {
+      rc = fetch_alloc((void**)&f.d_at, (size_t)f.cap * 8);
+      if (rc) return rc;
+    }
+    uint64_t all = ~0ull;
+    for (uint32_t r = 0; r < n; ++r) all &= (f.h_at[r] = offsets[r]);
+    if (all != RMQ_OFFSET_NONE) d_at = f.h_at;
+    if (d_at && dma_in) {
+      HIP_TRY(hipMemcpyAsync(f.d_at, f.h_at, (size_t)n * 8, hipMemcpyHostToDevice, e->copy_s));
+      d_at = f.d_at;
+    }
+  }
   if (dma_in) {
     HIP_TRY(hipMemcpyAsync(f.d_req, rows_pinned ? static_cast<const void*>(reqs) : static_cast<const void*>(f.h_req),
                            (size_t)n * sizeof(rmq_fetch_req), hipMemcpyHostToDevice, e->copy_s));
@@ -1859,7 +1886,10 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* max_by
     // another); anything else launches the held ones first, then itself
     // (nor does one with an RMQ_FETCH_VERIFY request: its third kernel follows its own gather)
     // (nor one with byte budgets: its trim kernel runs between its own resolve and gather)
-    const bool hold = !sync && !any && !verify && !d_bud && !dma && !e->profile && e->fetch_coalesce > 1;
+    // (nor one that passes an offsets array: only the single-ticket resolve reads them; an array
+    // whose entries are all RMQ_OFFSET_NONE is read by nothing and launches the plain resolve, but
+    // the call is still not held: FORMAT.md §7 says so of every call with offsets != NULL)
+    const bool hold = !sync && !any && !verify && !d_bud && !offsets && !dma && !e->profile && e->fetch_coalesce > 1;
     if (!hold) {
       rc = fetch_flush(e);
       if (rc) return rc;
@@ -1885,6 +1915,7 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* max_by
     // (a ticket with an RMQ_FETCH_VERIFY request: the verify kernel commits, after its verdicts)
     a.commits = any && !verify ? 1u : 0u;
     a.replica = replica ? 1u : 0u;
+    a.at = d_at;
     if (hold) {
       const size_t half = (size_t)f.csum_lines * kCsumStride;
       a.csum = f.d_csum + half * f.csum_par;
@@ -1983,12 +2014,17 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* max_by
 
 int rmq_fetch_async(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t mem, uint8_t* out,
                     uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket) {
-  return fetch_issue(e, reqs, nullptr, n, mem, out, out_cap, res, ticket, false);
+  return fetch_issue(e, reqs, nullptr, nullptr, n, mem, out, out_cap, res, ticket, false);
 }
 
 int rmq_fetch_bytes_async(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* max_bytes, uint32_t n,
                           uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket) {
-  return fetch_issue(e, reqs, max_bytes, n, mem, out, out_cap, res, ticket, false);
+  return fetch_issue(e, reqs, nullptr, max_bytes, n, mem, out, out_cap, res, ticket, false);
+}
+
+int rmq_fetch_at_async(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
+                       uint32_t n, uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket) {
+  return fetch_issue(e, reqs, offsets, max_bytes, n, mem, out, out_cap, res, ticket, false);
 }
 
 int rmq_fetch_poll(rmq_engine* e, uint64_t ticket, uint32_t wait, uint64_t* bytes_used) {
@@ -2016,7 +2052,7 @@ int rmq_fetch(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t mem
   if (!e) return RMQ_EINVAL;
   if (!n) return RMQ_OK;
   uint64_t t = 0;
-  const int rc = fetch_issue(e, reqs, nullptr, n, mem, out, out_cap, res, &t, true);
+  const int rc = fetch_issue(e, reqs, nullptr, nullptr, n, mem, out, out_cap, res, &t, true);
   if (rc) return rc;
   return rmq_fetch_poll(e, t, 1, bytes_used);
 }
@@ -2027,7 +2063,18 @@ int rmq_fetch_bytes(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* ma
   if (!e) return RMQ_EINVAL;
   if (!n) return RMQ_OK;
   uint64_t t = 0;
-  const int rc = fetch_issue(e, reqs, max_bytes, n, mem, out, out_cap, res, &t, true);
+  const int rc = fetch_issue(e, reqs, nullptr, max_bytes, n, mem, out, out_cap, res, &t, true);
+  if (rc) return rc;
+  return rmq_fetch_poll(e, t, 1, bytes_used);
+}
+
+int rmq_fetch_at(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
+                 uint32_t n, uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* bytes_used) {
+  if (bytes_used) *bytes_used = 0;
+  if (!e) return RMQ_EINVAL;
+  if (!n) return RMQ_OK;
+  uint64_t t = 0;
+  const int rc = fetch_issue(e, reqs, offsets, max_bytes, n, mem, out, out_cap, res, &t, true);
   if (rc) return rc;
   return rmq_fetch_poll(e, t, 1, bytes_used);
 }

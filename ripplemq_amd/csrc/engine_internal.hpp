@@ -350,6 +350,9 @@ struct rmq_engine {
     uint64_t* h_res = nullptr;   // pinned [cap][4] + {bytes needed, 0}
     uint32_t* h_bud = nullptr;   // pinned [cap] byte budgets of host rows (rmq_fetch_bytes), copied at the call
     uint32_t* d_bud = nullptr;   // [cap] their device copy where RMQ_FETCH_DMA moves the request rows
+    uint64_t* h_at = nullptr;    // pinned [cap] explicit offsets of host rows (rmq_fetch_at), copied at the call;
+                                 //   made by the slot's first call that passes offsets (as d_at)
+    uint64_t* d_at = nullptr;    // [cap] their device copy where RMQ_FETCH_DMA moves the request rows
     uint32_t cap = 0;
     uint8_t* d_out = nullptr;    // device staging of a host output
     uint64_t out_alloc = 0;

@@ -198,7 +198,11 @@ struct Resolved {
   int status;
 };
 
-__device__ __forceinline__ Resolved resolve_request(const FetchArgs& a, const uint4 rq, bool live) {
+// kAt (rmq_fetch_at, FORMAT.md §7 "Explicit offsets"): `at` is the request's explicit offset, or
+// RMQ_OFFSET_NONE for the table's; it replaces the table word once that has been loaded (the load
+// stays in the round of the partition's other words) and nothing after `off` knows the difference.
+template <bool kAt>
+__device__ __forceinline__ Resolved resolve_request(const FetchArgs& a, const uint4 rq, bool live, u64 at) {
   const DevState& st = a.st;
   const u32 p = rq.x, c = rq.y, mx = rq.z;
   int status = kOk;
@@ -210,7 +214,7 @@ __device__ __forceinline__ Resolved resolve_request(const FetchArgs& a, const ui
   const u32 lead = okp ? st.is_leader[pp] : 0u;
   // RMQ_FETCH_REPLICA: this engine's own replica, from its replica cursor, leader or follower
   const bool rep = a.replica && (rq.w & kFetchReplica);
-  const u64 off = okp ? (rep ? st.rcur[pp] : st.cons[(u64)pp * st.C + cc]) : 0ull;
+  const u64 tab = okp ? (rep ? st.rcur[pp] : st.cons[(u64)pp * st.C + cc]) : 0ull;
   const u64 hw = okp ? st.hw[pp] : 0ull;
   PartView v;
   v.leo = okp ? st.leo[pp] : 0ull;
@@ -222,6 +226,7 @@ __device__ __forceinline__ Resolved resolve_request(const FetchArgs& a, const ui
   const ulonglong2 ce = okp ? *reinterpret_cast<const ulonglong2*>(st.pcache + ((u64)pp * st.C + cc) * 2)
                             : make_ulonglong2(~0ull, 0ull);
   const u64 h_off = ce.x, h_pos = ce.y;
+  const u64 off = kAt && okp && at != ~0ull ? at : tab;
   v.rg = ring_ref(desc, st.interval_log2, st.icap_mul);
   v.ring = st.logs;
   bool need = false;  // the slice is not empty: both its ends are searched
@@ -280,8 +285,11 @@ template <bool kMulti>
 using FetchKArgs = typename std::conditional<kMulti, FetchBatch, FetchArgs>::type;  // (t[0] first in both)
 static_assert(offsetof(FetchBatch, t) == 0, "a batch's first ticket at the kernarg base");
 
-template <bool kMulti>
+// kAt: the single-ticket instantiation of a call with explicit offsets (a.at != null); the other
+// two never look at a.at.
+template <bool kMulti, bool kAt = false>
 __global__ __launch_bounds__(64 * kRW) void fetch_resolve_kernel(FetchKArgs<kMulti> batch) {
+  static_assert(!(kMulti && kAt), "a ticket with explicit offsets is launched alone");
   (void)batch;
   const FetchBatch& B = *(const FetchBatch*)__builtin_amdgcn_kernarg_segment_ptr();
   u32 bid = blockIdx.x;
@@ -293,16 +301,21 @@ __global__ __launch_bounds__(64 * kRW) void fetch_resolve_kernel(FetchKArgs<kMul
   // one PCIe read of 128 bytes instead of a 16-byte read per request), through LDS; the device
   // copy for the gather and the position cache
   __shared__ uint4 s_rq[kRW * kRPW];
+  // (kAt) and their explicit offsets beside them, by one load of consecutive 8-byte words (host
+  // rows: one more PCIe read of 128 bytes, in flight with the rows')
+  __shared__ u64 s_at[kAt ? kRW * kRPW : 1];
   {
     const u32 r0 = bid * kRW * kRPW + threadIdx.x;
     if (threadIdx.x < kRW * kRPW && r0 < a.n) {
       const uint4 x = *reinterpret_cast<const uint4*>(a.req + 4ull * r0);
+      if (kAt) s_at[threadIdx.x] = a.at[r0];
       s_rq[threadIdx.x] = x;
       if (a.req != a.req_dev) *reinterpret_cast<uint4*>(a.req_dev + 4ull * r0) = x;
     }
   }
   __syncthreads();
-  const Resolved q = resolve_request(a, live ? s_rq[w * kRPW + (lane >> 5)] : make_uint4(0, 0, 0, 0), live);
+  const Resolved q = resolve_request<kAt>(a, live ? s_rq[w * kRPW + (lane >> 5)] : make_uint4(0, 0, 0, 0), live,
+                                          kAt && live ? s_at[w * kRPW + (lane >> 5)] : ~0ull);
   __shared__ u64 s_b[kRW];
   const u64 b2 = bcast_u64(q.bytes, 0) + bcast_u64(q.bytes, 32);  // the wave's two requests
   if (lane == 0) s_b[w] = b2;
@@ -778,13 +791,18 @@ void preload_fetch_kernels() {
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_resolve_kernel<true>));
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_gather_kernel<true>));
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_trim_kernel));
+  (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_resolve_kernel<false, true>));
 }
 
 static void launch_batch(const FetchBatch& b, hipStream_t s, const hipEvent_t* e) {
   if (!b.rwg0[b.nt]) return;
   if (b.nt == 1) {  // one ticket: the 4x smaller kernarg, fixed offsets
-    hipExtLaunchKernelGGL(fetch_resolve_kernel<false>, dim3(b.rwg0[1]), dim3(64 * kRW), 0, s, e ? e[0] : nullptr,
-                          e ? e[1] : nullptr, 0, b.t[0]);
+    if (b.t[0].at)  // explicit offsets (rmq_fetch_at): the resolve that reads them
+      hipExtLaunchKernelGGL((fetch_resolve_kernel<false, true>), dim3(b.rwg0[1]), dim3(64 * kRW), 0, s,
+                            e ? e[0] : nullptr, e ? e[1] : nullptr, 0, b.t[0]);
+    else
+      hipExtLaunchKernelGGL(fetch_resolve_kernel<false>, dim3(b.rwg0[1]), dim3(64 * kRW), 0, s, e ? e[0] : nullptr,
+                            e ? e[1] : nullptr, 0, b.t[0]);
     hipExtLaunchKernelGGL(fetch_gather_kernel<false>, dim3(b.gwg0[1]), dim3(64 * kFW), 0, s, e ? e[2] : nullptr,
                           e ? e[3] : nullptr, 0, b.t[0]);
     return;
@@ -808,7 +826,11 @@ void launch_fetch_batch(const FetchArgs* t, uint32_t nt, hipStream_t s) {
 
 void launch_fetch_budget(const FetchArgs& a, const FetchTrimArgs& t, hipStream_t s) {
   if (!a.n) return;
-  hipLaunchKernelGGL(fetch_resolve_kernel<false>, dim3((a.n + kRW * kRPW - 1) / (kRW * kRPW)), dim3(64 * kRW), 0, s, a);
+  const dim3 rwgs((a.n + kRW * kRPW - 1) / (kRW * kRPW));
+  if (a.at)
+    hipLaunchKernelGGL((fetch_resolve_kernel<false, true>), rwgs, dim3(64 * kRW), 0, s, a);
+  else
+    hipLaunchKernelGGL(fetch_resolve_kernel<false>, rwgs, dim3(64 * kRW), 0, s, a);
   hipLaunchKernelGGL(fetch_trim_kernel, dim3((a.n + (kTT / 64) * kTQ - 1) / ((kTT / 64) * kTQ)), dim3(kTT), 0, s, t);
   hipLaunchKernelGGL(fetch_gather_kernel<false>, dim3((a.n + kGR - 1) / kGR), dim3(64 * kFW), 0, s, a);
 }

@@ -322,6 +322,9 @@ struct FetchArgs {
   uint32_t csum_lines;
   uint32_t commits;          // the host checked read-and-commit requests in the call (else flags ignored)
   uint32_t replica;          // the host checked RMQ_FETCH_REPLICA requests in the call (else flags ignored)
+  const uint64_t* at;        // [n] explicit offsets (rmq_fetch_at; RMQ_OFFSET_NONE: the table's), page-locked
+                             //   host or device memory, or null: none (only the single-ticket resolve
+                             //   launched for a ticket that has them reads this word)
 };
 constexpr uint32_t kFetchChunk = 256;  // requests per chunk sum (placement)
 // Up to kFetchBatch asynchronous fetches (tickets) are launched as one resolve + gather pair: ticket k

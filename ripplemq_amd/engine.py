@@ -46,6 +46,17 @@ def _budgets(max_bytes, n: int) -> np.ndarray | None:
     return np.ascontiguousarray(b, np.uint32)
 
 
+def _offsets(offsets, n: int) -> np.ndarray | None:
+    """The explicit offsets of n fetch requests as rmq_fetch_at takes them: an array, or one value for
+    every request; an entry None or RMQ_OFFSET_NONE: that request reads from its committed offset.
+    None: no offsets (rmq_fetch / rmq_fetch_bytes)."""
+    if offsets is None:
+        return None
+    if not np.isscalar(offsets) and not isinstance(offsets, np.ndarray):
+        offsets = [A.RMQ_OFFSET_NONE if o is None else int(o) for o in offsets]
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(offsets, np.uint64), (n,)), np.uint64)
+
+
 def _ptr_reused(a: np.ndarray) -> int:
     """_ptr of an array passed again and again (a fetch's request and result rows, views of
     page-locked memory from fetch_rows): numpy's .ctypes.data costs ~1.5 us a call, a checked cache
@@ -410,18 +421,24 @@ class Engine:
         return rc
 
     def fetch(self, pidx, consumer, max_records, out_cap: int | None = None, commit: bool = False,
-              out: np.ndarray | None = None, replica: bool = False, verify: bool = False, max_bytes=None):
+              out: np.ndarray | None = None, replica: bool = False, verify: bool = False, max_bytes=None,
+              offsets=None):
         """rmq_fetch into a host array (sized by a first call when out_cap is None, or the caller's
         uint8 `out`, e.g. page-locked from host_empty: one call, RMQ_ENOSPC if it is too small);
         commit: RMQ_FETCH_COMMIT on every request (the size query commits nothing); replica:
         RMQ_FETCH_REPLICA (this engine's own replica from its replica cursor, leader or follower);
         verify: RMQ_FETCH_VERIFY (a slice with a record that fails its checks comes back
         RMQ_ECORRUPT with count 0). max_bytes: a byte budget per request (an array, or one value
-        for all; 0: none): rmq_fetch_bytes, FORMAT.md §7."""
+        for all; 0: none): rmq_fetch_bytes, FORMAT.md §7. offsets: an explicit start offset per
+        request (an array, or one value for all; None or RMQ_OFFSET_NONE entries: the committed
+        offset): rmq_fetch_at, FORMAT.md §7; the size query reads at the same offsets."""
         n = len(pidx)
         bud = _budgets(max_bytes, n)
+        at = _offsets(offsets, n)
 
-        def call(*a):  # rmq_fetch, or rmq_fetch_bytes with the budgets after the requests
+        def call(*a):  # rmq_fetch, or rmq_fetch_bytes / rmq_fetch_at with their arrays after the requests
+            if at is not None:
+                return self.lib.rmq_fetch_at(a[0], a[1], _ptr(at), _ptr(bud), *a[2:])
             if bud is None:
                 return self.lib.rmq_fetch(*a)
             return self.lib.rmq_fetch_bytes(a[0], a[1], _ptr(bud), *a[2:])
@@ -455,7 +472,7 @@ class Engine:
 
     def fetch_device(self, pidx, consumer, max_records, d_out: int, out_cap: int, commit: bool = False,
                      req: np.ndarray | None = None, res: np.ndarray | None = None, pinned_rows: bool = False,
-                     d_rows: tuple | None = None, verify: bool = False, max_bytes=None):
+                     d_rows: tuple | None = None, verify: bool = False, max_bytes=None, offsets=None):
         """rmq_fetch into a device buffer (16-byte aligned); returns (rc, res, bytes_used). req / res:
         the caller's arrays (pidx / consumer / max_records None leave req's columns as they are);
         pinned_rows: page-locked ones (fetch_rows), read and written by the kernels in place
@@ -463,14 +480,19 @@ class Engine:
         device memory (RMQ_FETCH_DEVICE_ROWS, flags ignored), with an optional fourth element, the
         device array of the requests' byte budgets (uint32[n]); res is then None. verify:
         RMQ_FETCH_VERIFY on every request (host rows only). max_bytes: byte budgets of host rows, as
-        for fetch."""
+        for fetch. offsets: explicit offsets of host rows, as for fetch (rmq_fetch_at); with d_rows
+        the address of a device array (uint64[n], 8-byte aligned)."""
         if d_rows is not None:
             n, d_req, d_res = d_rows[:3]
             if max_bytes is not None:
                 raise ValueError("device rows take their budgets as d_rows' fourth element")
             used = C.c_uint64()
             mem = A.RMQ_MEM_DEVICE | A.RMQ_FETCH_DEVICE_ROWS
-            if len(d_rows) > 3 and d_rows[3]:
+            if offsets is not None:
+                rc = self.lib.rmq_fetch_at(self.h, C.c_void_p(d_req), C.c_void_p(int(offsets)),
+                                           C.c_void_p(d_rows[3] if len(d_rows) > 3 and d_rows[3] else None), n, mem,
+                                           d_out, out_cap, C.c_void_p(d_res), C.byref(used))
+            elif len(d_rows) > 3 and d_rows[3]:
                 rc = self.lib.rmq_fetch_bytes(self.h, C.c_void_p(d_req), C.c_void_p(d_rows[3]), n, mem,
                                               d_out, out_cap, C.c_void_p(d_res), C.byref(used))
             else:
@@ -493,7 +515,11 @@ class Engine:
         used = C.c_uint64()
         mem = A.RMQ_MEM_DEVICE | (A.RMQ_FETCH_PINNED_ROWS if pinned_rows else 0)
         bud = _budgets(max_bytes, n)
-        if bud is None:
+        at = _offsets(offsets, n)
+        if at is not None:
+            rc = self.lib.rmq_fetch_at(self.h, _ptr_reused(req), _ptr(at), _ptr(bud), n, mem, d_out, out_cap,
+                                       _ptr_reused(res), C.byref(used))
+        elif bud is None:
             rc = self.lib.rmq_fetch(self.h, _ptr_reused(req), n, mem, d_out, out_cap, _ptr_reused(res), C.byref(used))
         else:
             rc = self.lib.rmq_fetch_bytes(self.h, _ptr_reused(req), _ptr(bud), n, mem, d_out, out_cap,
@@ -505,7 +531,7 @@ class Engine:
     def fetch_async(self, pidx, consumer, max_records, d_out: int | None = None, out_cap: int = 0,
                     out: np.ndarray | None = None, req: np.ndarray | None = None,
                     res: np.ndarray | None = None, pinned_rows: bool = False,
-                    verify: bool = False, max_bytes=None) -> "FetchTicket":
+                    verify: bool = False, max_bytes=None, offsets=None) -> "FetchTicket":
         """rmq_fetch_async into a device buffer (d_out, 16-byte aligned) or a host array (out): the
         call returns at once; fetch_poll(ticket) gives (rc, res, bytes_used) once it completes. The
         handle keeps the request, result and output arrays alive until then. req ([n, 4] uint32)
@@ -514,7 +540,8 @@ class Engine:
         requests' flags, RMQ_FETCH_COMMIT). pinned_rows: req and res are page-locked (fetch_rows)
         and the kernels read and write them in place (RMQ_FETCH_PINNED_ROWS); req then stays
         unchanged until the ticket completes. verify: RMQ_FETCH_VERIFY ORed into every request.
-        max_bytes: byte budgets, as for fetch (rmq_fetch_bytes_async; read before the call returns)."""
+        max_bytes: byte budgets, as for fetch (rmq_fetch_bytes_async; read before the call returns).
+        offsets: explicit offsets, as for fetch (rmq_fetch_at_async; read before the call returns)."""
         n = len(pidx) if pidx is not None else len(req)
         if pinned_rows and (req is None or res is None):
             raise ValueError("pinned_rows needs the caller's page-locked req and res (fetch_rows)")
@@ -537,7 +564,11 @@ class Engine:
             mem |= A.RMQ_FETCH_PINNED_ROWS
         t = C.c_uint64()
         bud = _budgets(max_bytes, n)
-        if bud is None:
+        at = _offsets(offsets, n)
+        if at is not None:
+            _check(self.lib.rmq_fetch_at_async(self.h, _ptr_reused(req), _ptr(at), _ptr(bud), n, mem, ptr, out_cap,
+                                               _ptr_reused(res), C.byref(t)), "rmq_fetch_at_async")
+        elif bud is None:
             _check(self.lib.rmq_fetch_async(self.h, _ptr_reused(req), n, mem, ptr, out_cap, _ptr_reused(res), C.byref(t)),
                    "rmq_fetch_async")
         else:
