@@ -378,9 +378,28 @@ int rmq_fetch(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t mem
    res is written before the poll that returns the result.
    mem | RMQ_FETCH_DEVICE_ROWS (ABI 9; rmq_fetch too): reqs and res are device memory (a broker whose
    requests arrive on the GPU): no transfer at all. The host never sees these requests, so their
-   flags word must be 0 (RMQ_FETCH_COMMIT needs host rows: the call checks them) and is ignored. */
+   flags word must be 0 (RMQ_FETCH_COMMIT needs host rows: the call checks them) and is ignored.
+   mem | RMQ_FETCH_FILL (added after ABI 11 without a version bump; every fetch entry point, with
+   ordinary, pinned or device rows; FORMAT.md §7 "Filling a bounded output"; a Kafka fetch request's
+   fetch.max.bytes): out_cap bounds the whole call instead of failing it. Answer the call with an
+   unlimited out_cap (budgets and explicit offsets applied): row r has B_r bytes, P_r before it. If
+   everything fits out_cap, the call is answered exactly as without the flag. Otherwise, with r* the
+   first request with P_r + B_r > out_cap: the requests before r* are unchanged; r* is answered as
+   rmq_fetch_bytes answers a budget of out_cap - P_r* (cut at the last record boundary inside it;
+   count, bytes, commit and verify follow the cut; if not even its first record fits: count 0,
+   bytes 0, nothing committed, that record's size in `reserved`, status RMQ_ENOSPC when P_r* = 0,
+   the output itself being too small, else RMQ_PENDING); every later request that would have been
+   served bytes is status RMQ_PENDING, start_offset as resolved, count 0, bytes 0, reserved 0: it
+   takes no output and commits nothing (ask again); later rows without bytes (empty, RMQ_EOFFSET,
+   errors, budget RMQ_ENOSPC) are unchanged. out_pos is the running sum of the final bytes,
+   bytes_used <= out_cap, and the call returns RMQ_OK: no row is answered RMQ_ENOSPC for capacity.
+   out == NULL with out_cap == 0 names the first record's size of the first request with records
+   (RMQ_ENOSPC, `reserved`). Requests are served in request order: a caller that rotates its order
+   from call to call is fair to all. A filling call is never held back to go with later
+   asynchronous fetches. */
 #define RMQ_FETCH_PINNED_ROWS 0x100u
 #define RMQ_FETCH_DEVICE_ROWS 0x200u
+#define RMQ_FETCH_FILL 0x400u
 int rmq_fetch_async(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t mem, uint8_t* out,
                     uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket);
 /* Completion of an rmq_fetch_async ticket: RMQ_PENDING while it runs (wait != 0: block instead), else

@@ -21,6 +21,7 @@ RMQ_FETCH_REPLICA = 2
 RMQ_FETCH_VERIFY = 0x20
 RMQ_FETCH_PINNED_ROWS = 0x100
 RMQ_FETCH_DEVICE_ROWS = 0x200
+RMQ_FETCH_FILL = 0x400
 RMQ_MAX_RF = 8
 RMQ_ALL_PARTITIONS = 0xFFFFFFFF
 RMQ_OFFSET_NONE = 0xFFFFFFFFFFFFFFFF

@@ -590,7 +590,7 @@ void free_engine(rmq_engine* e) {
   repair_remote_free(e);
   if (e->state_stage) hipHostFree(e->state_stage);
   for (rmq_engine::FetchSlot& f : e->fslot) {
-    void* fs[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_out, f.d_bud, f.d_at};
+    void* fs[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_out, f.d_bud, f.d_at, f.d_csum_fill};
     for (void* p : fs) bufs.push_back(p);
     if (f.h_bud) hipHostFree(f.h_bud);
     if (f.h_at) hipHostFree(f.h_at);
@@ -1621,7 +1621,7 @@ int fetch_alloc(void** p, size_t bytes) {
 
 int fetch_slot_reserve(rmq_engine::FetchSlot& f, uint32_t n, uint64_t stage, hipStream_t s) {
   if (n > f.cap) {
-    void* ds[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_bud, f.d_at};
+    void* ds[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_bud, f.d_at, f.d_csum_fill};
     for (void* p : ds)
       if (p) hipFree(p);
     if (f.h_req) hipHostFree(f.h_req);
@@ -1629,7 +1629,7 @@ int fetch_slot_reserve(rmq_engine::FetchSlot& f, uint32_t n, uint64_t stage, hip
     if (f.h_bud) hipHostFree(f.h_bud);
     if (f.h_at) hipHostFree(f.h_at);
     f.d_req = f.d_cpre = f.h_req = f.h_bud = f.d_bud = nullptr;
-    f.d_res = f.d_aux = f.d_csum = f.h_res = f.h_at = f.d_at = nullptr;
+    f.d_res = f.d_aux = f.d_csum = f.h_res = f.h_at = f.d_at = f.d_csum_fill = nullptr;
     f.cap = 0;
     const uint32_t cap = std::max<uint32_t>(n, 1024);
     int rc = fetch_alloc((void**)&f.d_req, (size_t)cap * 16);
@@ -1734,7 +1734,8 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offset
   if (!e || !ticket) return RMQ_EINVAL;
   bool rows_pinned = (mem & RMQ_FETCH_PINNED_ROWS) != 0;
   const bool rows_dev = (mem & RMQ_FETCH_DEVICE_ROWS) != 0;
-  mem &= ~(RMQ_FETCH_PINNED_ROWS | RMQ_FETCH_DEVICE_ROWS);
+  const bool fill = (mem & RMQ_FETCH_FILL) != 0;  // (FORMAT.md §7 "Filling a bounded output")
+  mem &= ~(RMQ_FETCH_PINNED_ROWS | RMQ_FETCH_DEVICE_ROWS | RMQ_FETCH_FILL);
   if (rows_dev && (rows_pinned || mem != RMQ_MEM_DEVICE)) return RMQ_EINVAL;  // (output on the device too)
   if (rows_dev && (reinterpret_cast<uintptr_t>(max_bytes) & 3u)) return RMQ_EINVAL;
   if (rows_dev && (reinterpret_cast<uintptr_t>(offsets) & 7u)) return RMQ_EINVAL;
@@ -1869,6 +1870,12 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offset
       d_at = f.d_at;
     }
   }
+  // (the chunk sums a filling call's gather reads: made by the slot's first filling call, as the
+  // offset words; fetch_slot_reserve frees them when the slot grows)
+  if (fill && !f.d_csum_fill) {
+    rc = fetch_alloc((void**)&f.d_csum_fill, (size_t)f.csum_lines * kCsumStride * 8);
+    if (rc) return rc;
+  }
   if (dma_in) {
     HIP_TRY(hipMemcpyAsync(f.d_req, rows_pinned ? static_cast<const void*>(reqs) : static_cast<const void*>(f.h_req),
                            (size_t)n * sizeof(rmq_fetch_req), hipMemcpyHostToDevice, e->copy_s));
@@ -1889,7 +1896,9 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offset
     // (nor one that passes an offsets array: only the single-ticket resolve reads them; an array
     // whose entries are all RMQ_OFFSET_NONE is read by nothing and launches the plain resolve, but
     // the call is still not held: FORMAT.md §7 says so of every call with offsets != NULL)
-    const bool hold = !sync && !any && !verify && !d_bud && !offsets && !dma && !e->profile && e->fetch_coalesce > 1;
+    // (nor one that fills its output: its fill kernel runs before its own gather)
+    const bool hold =
+        !sync && !any && !verify && !d_bud && !offsets && !fill && !dma && !e->profile && e->fetch_coalesce > 1;
     if (!hold) {
       rc = fetch_flush(e);
       if (rc) return rc;
@@ -1933,11 +1942,11 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offset
     // (profiling replays a fetch's kernels back to back; a committing fetch runs once: each run
     // would commit again and the next would read from the committed offset)
     // (nor is a verifying one replayed: its third kernel rewrites the rows the gather wrote)
-    // (nor a budgeted one: its three kernels are launched without dispatch spans)
-    const uint32_t runs = hold ? 0u : e->profile && !any && !verify && !d_bud ? e->fetch_replay : 1u;
+    // (nor a budgeted one: its three kernels are launched without dispatch spans; nor a filling one)
+    const uint32_t runs = hold ? 0u : e->profile && !any && !verify && !d_bud && !fill ? e->fetch_replay : 1u;
     // (a committing fetch records no dispatch spans: the events the kernels' own dispatches record
     // were measured to hold the second kernel ~10 us behind the first, which its one run would carry)
-    const bool spans = e->profile && !any && !verify && !d_bud;
+    const bool spans = e->profile && !any && !verify && !d_bud && !fill;
     if (e->profile) {  // kernel 3: the first run's dispatch spans; 4: every run
       if (spans) {
         for (hipEvent_t& x : ev) x = pool_event(e);
@@ -1954,7 +1963,7 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offset
       a.csum = f.d_csum + half * f.csum_par;
       a.csum_next = f.d_csum + half * (f.csum_par ^ 1u);
       f.csum_par ^= 1u;
-      if (d_bud) {  // resolve, trim, gather
+      if (d_bud || fill) {  // resolve, trim (budgets), fill (a filling call), gather
         FetchTrimArgs t{};
         t.st = e->st;
         t.budget = d_bud;
@@ -1964,7 +1973,16 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offset
         t.cpre = f.d_cpre;
         t.csum = a.csum;
         t.n = n;
-        launch_fetch_budget(a, t, e->main_s);
+        if (fill) {
+          FetchFillArgs ff{};
+          ff.t = t;
+          ff.csum_out = f.d_csum_fill;
+          ff.out_cap = out_cap;
+          ff.verify = verify ? 1u : 0u;
+          launch_fetch_fill(a, ff, e->main_s);
+        } else {
+          launch_fetch_budget(a, t, e->main_s);
+        }
       } else {
         launch_fetch(a, e->main_s, spans && k == 0 ? ev : nullptr);
       }

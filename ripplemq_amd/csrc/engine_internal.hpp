@@ -344,6 +344,9 @@ struct rmq_engine {
     uint32_t* d_cpre = nullptr;
     uint64_t* d_csum = nullptr;   // two halves of csum_lines lines: a fetch adds into one, its gather
                                   // zeroes the other for the next fetch of the slot (same stream)
+    uint64_t* d_csum_fill = nullptr;  // csum_lines lines more: the chunk sums a filling call's fill kernel
+                                      //   writes whole for its gather (RMQ_FETCH_FILL); made by the slot's
+                                      //   first filling call
     uint32_t csum_lines = 0;
     uint32_t csum_par = 0;
     uint32_t* h_req = nullptr;   // pinned

@@ -25,6 +25,10 @@
 //          start inside the budget, found from the position-keyed sparse index and a walk of the
 //          length words up to the limit, and the words the gather places and copies from are
 //          rewritten.
+//  fill    (only a ticket with RMQ_FETCH_FILL; before the gather; a workgroup per chunk of 256
+//          requests): out_cap bounds the whole call: a prefix scan over the requests' bytes finds
+//          the request that crosses the end of the output, which is cut by the trim's own search
+//          and walk; the served requests after it are put off (RMQ_PENDING).
 //
 // The kernels (resolve, gather; the chunk sums a slot's previous gather cleared) run on the
 // pipeline stream itself, after the last pipeline launch the host had issued and before the next
@@ -531,18 +535,18 @@ __device__ __forceinline__ WinWords load_window_to(const uint8_t* ring, u64 wb, 
 // address masked into the ring, stops at the first record that ends past the limit and never
 // counts the slice's last record, so a damaged length word cuts early and is never followed out
 // of the slice.
-__global__ __launch_bounds__(kTT) void fetch_trim_kernel(FetchTrimArgs a) {
+// The cut itself, shared by the trim and the fill kernel: the whole wave calls it, quarter q cuts
+// request r (quarter-uniform) at budget b when act (the caller has checked: served RMQ_OK with
+// count > 0 records, bytes > b), rewrites the row's words, cpre and the position cache entry, and
+// returns the k* records and bytes kept. zst: the status of a row of which not even the first
+// record fits (its size goes into `reserved`).
+struct TrimCut {
+  u64 k, nb;
+};
+__device__ __forceinline__ TrimCut trim_request(const FetchTrimArgs& a, u32 r, bool act, u64 b, u64 count, u64 bytes,
+                                                int zst) {
   const DevState& st = a.st;
   const u32 lane = lane_id(), q = lane / kQL, hl = lane % kQL;
-  const u32 r0 = (blockIdx.x * (kTT / 64) + (threadIdx.x >> 6)) * kTQ;  // the wave's first request
-  const u32 r = r0 + q;
-  const bool live = r < a.n;
-  // one read of the request's words (the same address in the 16 lanes of a quarter)
-  const u32 b = live ? a.budget[r] : 0u;
-  const u64 w2 = live ? a.res[4ull * r + 2] : 0ull, w3 = live ? a.res[4ull * r + 3] : 0ull;
-  const u64 count = (u32)w2, bytes = w2 >> 32;
-  const bool act = live && b != 0u && (int)(u32)w3 == kOk && count > 0 && bytes > (u64)b;
-  if (!__any(act)) return;
   const u64 off = act ? a.res[4ull * r] : 0ull;
   const u64 pos0 = act ? a.aux[2ull * r] : 0ull, rw = act ? a.aux[2ull * r + 1] : 0ull;
   const u32 p = act ? a.req_dev[4ull * r] : 0u, c = act ? a.req_dev[4ull * r + 1] : 0u;  // (served: in range)
@@ -551,7 +555,7 @@ __global__ __launch_bounds__(kTT) void fetch_trim_kernel(FetchTrimArgs a) {
   const uint8_t* ring = st.logs + (rw >> 6);
   const u64 mask = (1ull << (rw & 63ull)) - 1ull;
   const u64* E = st.index + rg.ibase * 2;
-  const u64 limit = pos0 + (u64)(b & ~15u);
+  const u64 limit = pos0 + (b & ~15ull);
   constexpr u32 kQMask = (1u << kQL) - 1u;
   // the index entry to start from (quarter-uniform state)
   u64 c_off = off, c_pos = pos0;
@@ -620,18 +624,109 @@ __global__ __launch_bounds__(kTT) void fetch_trim_kernel(FetchTrimArgs a) {
   const u64 nb = k ? wb + 16ull * cur - pos0 : 0ull;  // the trimmed slice's bytes
   if (act && hl == 0) {
     a.res[4ull * r + 2] = k | (nb << 32);
-    // no record fits: RMQ_ENOSPC for this request alone, the first record's size in `reserved`
-    if (!k) a.res[4ull * r + 3] = (u64)(uint32_t)kNoSpc | ((rs_last < bytes ? rs_last : bytes) << 32);
+    // no record fits: not served (zst) for this request alone, the first record's size in `reserved`
+    if (!k) a.res[4ull * r + 3] = (u64)(uint32_t)zst | ((rs_last < bytes ? rs_last : bytes) << 32);
     a.cpre[r] = (u32)nb;
     *reinterpret_cast<ulonglong2*>(st.pcache + ((u64)p * st.C + c) * 2) = make_ulonglong2(off + k, pos0 + nb);
   }
+  return TrimCut{k, nb};
+}
+
+// The trim kernel: every budgeted request that is served more than its budget is cut.
+__global__ __launch_bounds__(kTT) void fetch_trim_kernel(FetchTrimArgs a) {
+  const u32 lane = lane_id(), q = lane / kQL;
+  const u32 r0 = (blockIdx.x * (kTT / 64) + (threadIdx.x >> 6)) * kTQ;  // the wave's first request
+  const u32 r = r0 + q;
+  const bool live = r < a.n;
+  // one read of the request's words (the same address in the 16 lanes of a quarter)
+  const u32 b = live ? a.budget[r] : 0u;
+  const u64 w2 = live ? a.res[4ull * r + 2] : 0ull, w3 = live ? a.res[4ull * r + 3] : 0ull;
+  const u64 count = (u32)w2, bytes = w2 >> 32;
+  const bool act = live && b != 0u && (int)(u32)w3 == kOk && count > 0 && bytes > (u64)b;
+  if (!__any(act)) return;
+  const TrimCut t = trim_request(a, r, act, b, count, bytes, kNoSpc);
   // the bytes removed leave the chunk's sum: one subtract per wave (its requests share a chunk)
   static_assert(kFetchChunk % kTQ == 0, "a trim wave never straddles a chunk");
-  u64 cut = act ? bytes - nb : 0ull, cut_w = 0;
+  u64 cut = act ? bytes - t.nb : 0ull, cut_w = 0;
 #pragma unroll
   for (u32 j = 0; j < kTQ; ++j) cut_w += bcast_u64(cut, kQL * j);
   if (lane == 0 && cut_w)
     atomicAdd((unsigned long long*)&a.csum[(u64)(r0 / kFetchChunk) * kCsumStride], (unsigned long long)(0ull - cut_w));
+}
+
+// ---------------------------------------------------------------------------------------------
+// RMQ_FETCH_FILL (FORMAT.md §7 "Filling a bounded output"): the kernel before the gather of a ticket
+// that fills its output
+// ---------------------------------------------------------------------------------------------
+constexpr int kPending = 1;  // RMQ_PENDING
+
+// A workgroup per chunk of kFetchChunk requests, a thread per request; every chunk decides alone.
+// With B_r = cpre[r] (not zero for exactly the rows served RMQ_OK with records, the trim's cuts
+// applied) and P_r the bytes of the requests before r (the chunk sums before the chunk, then a scan
+// of the chunk's cpre), the request that crosses the end of the output is the one with B_r > 0,
+// P_r <= out_cap < P_r + B_r (the sums rise with r, so there is at most one and every row knows
+// by itself which side of it it stands on): it is cut at budget out_cap - P_r by the trim's own
+// search and walk (quarter 0 of wave 0), and every served row after it (P_r > out_cap) becomes
+// RMQ_PENDING with the true pair {its offset, that offset's position} back in the position cache.
+// A chunk wholly inside the output changes nothing, one wholly past it holds pending rows only.
+// The chunk sums are read in t.csum and written, every chunk's, to csum_out, which no workgroup
+// of this kernel reads: a chunk's new sum never meets another workgroup's read of its old one.
+__global__ __launch_bounds__(kFetchChunk) void fetch_fill_kernel(FetchFillArgs a) {
+  static_assert(kFetchChunk == 256, "four waves, a thread per request of the chunk");
+  const FetchTrimArgs& t = a.t;
+  const u32 c = blockIdx.x, tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
+  __shared__ u64 s_sum[kFetchChunk / 64];
+  __shared__ u64 s_cutp;  // P of the crossing request
+  __shared__ u32 s_cutr;  // its index (~0: none)
+  // bytes before the chunk (every wave on its own: at most a few loads per lane, L2-resident)
+  u64 base = 0;
+  for (u32 k = lane; k < c; k += 64) base += t.csum[(u64)k * kCsumStride];
+  base = bcast_u64(wave_incl_scan(base), 63);
+  const u64 own = t.csum[(u64)c * kCsumStride];
+  if (base + own <= a.out_cap) {  // (workgroup-uniform) wholly inside: as resolved
+    if (tid == 0) a.csum_out[(u64)c * kCsumStride] = own;
+    return;
+  }
+  const u32 r = c * kFetchChunk + tid;
+  const u64 nb = r < t.n ? t.cpre[r] : 0ull;
+  const u64 inc = wave_incl_scan(nb);
+  if (lane == 63) s_sum[w] = inc;
+  if (tid == 0) s_cutr = ~0u;
+  __syncthreads();
+  u64 P = base + inc - nb;
+  for (u32 k = 0; k < w; ++k) P += s_sum[k];
+  const bool pend = nb && P > a.out_cap;
+  if (nb && P <= a.out_cap && P + nb > a.out_cap) {
+    s_cutr = r;
+    s_cutp = P;
+  }
+  if (pend) {
+    const u32 p = t.req_dev[4ull * r], cn = t.req_dev[4ull * r + 1];  // (served: in range)
+    const bool vf = a.verify && (t.req_dev[4ull * r + 3] & kFetchVerify);
+    const u64 off = t.res[4ull * r], pos0 = t.aux[2ull * r];
+    t.res[4ull * r + 2] = 0;
+    t.res[4ull * r + 3] = (u64)(uint32_t)kPending;
+    t.cpre[r] = 0;
+    // (a flagged request that is not served leaves no entry, as the verify kernel has it: FORMAT.md §10)
+    *reinterpret_cast<ulonglong2*>(t.st.pcache + ((u64)p * t.st.C + cn) * 2) =
+        vf ? make_ulonglong2(~0ull, 0ull) : make_ulonglong2(off, pos0);
+  }
+  __syncthreads();
+  if (w != 0) return;
+  const u32 rc = s_cutr;
+  const bool act = rc != ~0u && lane < kQL;
+  u64 kept = base > a.out_cap ? 0ull : own;  // (no crossing request: only if the sums disagree with cpre)
+  if (rc != ~0u) {
+    const u64 Pc = s_cutp;
+    const u64 w2 = t.res[4ull * rc + 2];
+    // an output that cannot hold the call's first record: RMQ_ENOSPC, the capacity that would in `reserved`
+    const TrimCut x = trim_request(t, rc, act, a.out_cap - Pc, (u32)w2, w2 >> 32, Pc ? kPending : kNoSpc);
+    if (lane == 0 && !x.k && a.verify && (t.req_dev[4ull * rc + 3] & kFetchVerify))
+      *reinterpret_cast<ulonglong2*>(t.st.pcache + ((u64)t.req_dev[4ull * rc] * t.st.C + t.req_dev[4ull * rc + 1]) * 2) =
+          make_ulonglong2(~0ull, 0ull);
+    kept = Pc - base + bcast_u64(x.nb, 0);
+  }
+  if (lane == 0) a.csum_out[(u64)c * kCsumStride] = kept;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -792,6 +887,7 @@ void preload_fetch_kernels() {
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_gather_kernel<true>));
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_trim_kernel));
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_resolve_kernel<false, true>));
+  (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_fill_kernel));
 }
 
 static void launch_batch(const FetchBatch& b, hipStream_t s, const hipEvent_t* e) {
@@ -833,6 +929,21 @@ void launch_fetch_budget(const FetchArgs& a, const FetchTrimArgs& t, hipStream_t
     hipLaunchKernelGGL(fetch_resolve_kernel<false>, rwgs, dim3(64 * kRW), 0, s, a);
   hipLaunchKernelGGL(fetch_trim_kernel, dim3((a.n + (kTT / 64) * kTQ - 1) / ((kTT / 64) * kTQ)), dim3(kTT), 0, s, t);
   hipLaunchKernelGGL(fetch_gather_kernel<false>, dim3((a.n + kGR - 1) / kGR), dim3(64 * kFW), 0, s, a);
+}
+
+void launch_fetch_fill(const FetchArgs& a, const FetchFillArgs& f, hipStream_t s) {
+  if (!a.n) return;
+  const dim3 rwgs((a.n + kRW * kRPW - 1) / (kRW * kRPW));
+  if (a.at)
+    hipLaunchKernelGGL((fetch_resolve_kernel<false, true>), rwgs, dim3(64 * kRW), 0, s, a);
+  else
+    hipLaunchKernelGGL(fetch_resolve_kernel<false>, rwgs, dim3(64 * kRW), 0, s, a);
+  if (f.t.budget)
+    hipLaunchKernelGGL(fetch_trim_kernel, dim3((a.n + (kTT / 64) * kTQ - 1) / ((kTT / 64) * kTQ)), dim3(kTT), 0, s, f.t);
+  hipLaunchKernelGGL(fetch_fill_kernel, dim3((a.n + kFetchChunk - 1) / kFetchChunk), dim3(kFetchChunk), 0, s, f);
+  FetchArgs g = a;  // the gather places from the sums the fill kernel wrote
+  g.csum = f.csum_out;
+  hipLaunchKernelGGL(fetch_gather_kernel<false>, dim3((a.n + kGR - 1) / kGR), dim3(64 * kFW), 0, s, g);
 }
 
 void launch_fetch(const FetchArgs& a, hipStream_t s, const hipEvent_t* ev) {

@@ -370,7 +370,20 @@ struct FetchTrimArgs {
   uint32_t n;
   uint32_t pad;
 };
-
+// The kernel before the gather of a ticket that fills a bounded output (RMQ_FETCH_FILL, FORMAT.md §7
+// "Filling a bounded output"; after the trim when the ticket has budgets too): requests are served
+// whole in request order while they fit in out_cap, the one that crosses the end is cut at a record
+// boundary (the trim's cut, budget = what is left), the served ones after it become RMQ_PENDING.
+// It rewrites the same words as the trim, but the chunk sums: those go, every word of them, to
+// csum_out, which the ticket's gather reads instead (a workgroup reads the sums of the chunks before
+// its own in t.csum, so none of those may change under it).
+struct FetchFillArgs {
+  FetchTrimArgs t;           // (budget unused)
+  uint64_t* csum_out;        // [chunks of n][kCsumStride] the chunk sums after filling
+  uint64_t out_cap;
+  uint32_t verify;           // the host checked RMQ_FETCH_VERIFY requests in the call (else flags ignored)
+  uint32_t pad;
+};
 
 
 struct ConsumerCommitArgs {  // one item per (partition, consumer): the host resolved last-writer-wins
@@ -596,6 +609,9 @@ void launch_fetch(const FetchArgs& a, hipStream_t s, const hipEvent_t* ev4);
 void launch_fetch_batch(const FetchArgs* t, uint32_t nt, hipStream_t s);  // nt <= kFetchBatch tickets, one pair
 // One ticket with byte budgets: resolve, trim, gather (t's res, aux, cpre, csum are a's).
 void launch_fetch_budget(const FetchArgs& a, const FetchTrimArgs& t, hipStream_t s);
+// One ticket that fills its output: resolve, trim (budgets: f.t.budget not null), fill, gather
+// (a.csum is what the resolve adds into; the gather reads f.csum_out).
+void launch_fetch_fill(const FetchArgs& a, const FetchFillArgs& f, hipStream_t s);
 void launch_fetch_verify(const FetchVerifyArgs& a, uint32_t max_wgs, hipStream_t s);  // after the ticket's gather
 void preload_fetch_kernels();
 

@@ -422,7 +422,7 @@ class Engine:
 
     def fetch(self, pidx, consumer, max_records, out_cap: int | None = None, commit: bool = False,
               out: np.ndarray | None = None, replica: bool = False, verify: bool = False, max_bytes=None,
-              offsets=None):
+              offsets=None, fill: bool = False):
         """rmq_fetch into a host array (sized by a first call when out_cap is None, or the caller's
         uint8 `out`, e.g. page-locked from host_empty: one call, RMQ_ENOSPC if it is too small);
         commit: RMQ_FETCH_COMMIT on every request (the size query commits nothing); replica:
@@ -431,10 +431,15 @@ class Engine:
         RMQ_ECORRUPT with count 0). max_bytes: a byte budget per request (an array, or one value
         for all; 0: none): rmq_fetch_bytes, FORMAT.md §7. offsets: an explicit start offset per
         request (an array, or one value for all; None or RMQ_OFFSET_NONE entries: the committed
-        offset): rmq_fetch_at, FORMAT.md §7; the size query reads at the same offsets."""
+        offset): rmq_fetch_at, FORMAT.md §7; the size query reads at the same offsets. fill:
+        RMQ_FETCH_FILL (FORMAT.md §7 "Filling a bounded output": requests are served in order until
+        the output is full, the rest come back RMQ_PENDING); needs out_cap or out (no sizing call)."""
         n = len(pidx)
+        if fill and out is None and out_cap is None:
+            raise ValueError("fill needs out_cap or out: a filling fetch has no sizing call")
         bud = _budgets(max_bytes, n)
         at = _offsets(offsets, n)
+        host = A.RMQ_MEM_HOST | (A.RMQ_FETCH_FILL if fill else 0)
 
         def call(*a):  # rmq_fetch, or rmq_fetch_bytes / rmq_fetch_at with their arrays after the requests
             if at is not None:
@@ -451,7 +456,7 @@ class Engine:
             if commit:
                 req[:, 3] |= A.RMQ_FETCH_COMMIT
             used = C.c_uint64()
-            rc = call(self.h, _ptr(req), n, A.RMQ_MEM_HOST, _ptr(out), out.size, _ptr(res), C.byref(used))
+            rc = call(self.h, _ptr(req), n, host, _ptr(out), out.size, _ptr(res), C.byref(used))
             if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
                 raise EngineError(rc, "rmq_fetch")
             return rc, res, out, int(used.value)
@@ -465,14 +470,15 @@ class Engine:
             req[:, 3] |= A.RMQ_FETCH_COMMIT
         out = np.zeros(max(out_cap, 1), np.uint8)
         used = C.c_uint64()
-        rc = call(self.h, _ptr(req), n, A.RMQ_MEM_HOST, _ptr(out), out_cap, _ptr(res), C.byref(used))
+        rc = call(self.h, _ptr(req), n, host, _ptr(out), out_cap, _ptr(res), C.byref(used))
         if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
             raise EngineError(rc, "rmq_fetch")
         return rc, res, out[:out_cap], int(used.value)
 
     def fetch_device(self, pidx, consumer, max_records, d_out: int, out_cap: int, commit: bool = False,
                      req: np.ndarray | None = None, res: np.ndarray | None = None, pinned_rows: bool = False,
-                     d_rows: tuple | None = None, verify: bool = False, max_bytes=None, offsets=None):
+                     d_rows: tuple | None = None, verify: bool = False, max_bytes=None, offsets=None,
+                     fill: bool = False):
         """rmq_fetch into a device buffer (16-byte aligned); returns (rc, res, bytes_used). req / res:
         the caller's arrays (pidx / consumer / max_records None leave req's columns as they are);
         pinned_rows: page-locked ones (fetch_rows), read and written by the kernels in place
@@ -481,13 +487,14 @@ class Engine:
         device array of the requests' byte budgets (uint32[n]); res is then None. verify:
         RMQ_FETCH_VERIFY on every request (host rows only). max_bytes: byte budgets of host rows, as
         for fetch. offsets: explicit offsets of host rows, as for fetch (rmq_fetch_at); with d_rows
-        the address of a device array (uint64[n], 8-byte aligned)."""
+        the address of a device array (uint64[n], 8-byte aligned). fill: RMQ_FETCH_FILL, as for fetch
+        (every kind of rows)."""
         if d_rows is not None:
             n, d_req, d_res = d_rows[:3]
             if max_bytes is not None:
                 raise ValueError("device rows take their budgets as d_rows' fourth element")
             used = C.c_uint64()
-            mem = A.RMQ_MEM_DEVICE | A.RMQ_FETCH_DEVICE_ROWS
+            mem = A.RMQ_MEM_DEVICE | A.RMQ_FETCH_DEVICE_ROWS | (A.RMQ_FETCH_FILL if fill else 0)
             if offsets is not None:
                 rc = self.lib.rmq_fetch_at(self.h, C.c_void_p(d_req), C.c_void_p(int(offsets)),
                                            C.c_void_p(d_rows[3] if len(d_rows) > 3 and d_rows[3] else None), n, mem,
@@ -513,7 +520,7 @@ class Engine:
         if res is None:
             res = np.zeros(n, FETCH_RES_DTYPE)
         used = C.c_uint64()
-        mem = A.RMQ_MEM_DEVICE | (A.RMQ_FETCH_PINNED_ROWS if pinned_rows else 0)
+        mem = A.RMQ_MEM_DEVICE | (A.RMQ_FETCH_PINNED_ROWS if pinned_rows else 0) | (A.RMQ_FETCH_FILL if fill else 0)
         bud = _budgets(max_bytes, n)
         at = _offsets(offsets, n)
         if at is not None:
@@ -531,7 +538,7 @@ class Engine:
     def fetch_async(self, pidx, consumer, max_records, d_out: int | None = None, out_cap: int = 0,
                     out: np.ndarray | None = None, req: np.ndarray | None = None,
                     res: np.ndarray | None = None, pinned_rows: bool = False,
-                    verify: bool = False, max_bytes=None, offsets=None) -> "FetchTicket":
+                    verify: bool = False, max_bytes=None, offsets=None, fill: bool = False) -> "FetchTicket":
         """rmq_fetch_async into a device buffer (d_out, 16-byte aligned) or a host array (out): the
         call returns at once; fetch_poll(ticket) gives (rc, res, bytes_used) once it completes. The
         handle keeps the request, result and output arrays alive until then. req ([n, 4] uint32)
@@ -541,7 +548,8 @@ class Engine:
         and the kernels read and write them in place (RMQ_FETCH_PINNED_ROWS); req then stays
         unchanged until the ticket completes. verify: RMQ_FETCH_VERIFY ORed into every request.
         max_bytes: byte budgets, as for fetch (rmq_fetch_bytes_async; read before the call returns).
-        offsets: explicit offsets, as for fetch (rmq_fetch_at_async; read before the call returns)."""
+        offsets: explicit offsets, as for fetch (rmq_fetch_at_async; read before the call returns).
+        fill: RMQ_FETCH_FILL, as for fetch."""
         n = len(pidx) if pidx is not None else len(req)
         if pinned_rows and (req is None or res is None):
             raise ValueError("pinned_rows needs the caller's page-locked req and res (fetch_rows)")
@@ -562,6 +570,8 @@ class Engine:
             mem, ptr = A.RMQ_MEM_HOST, (_ptr(out) if out is not None else None)
         if pinned_rows:
             mem |= A.RMQ_FETCH_PINNED_ROWS
+        if fill:
+            mem |= A.RMQ_FETCH_FILL
         t = C.c_uint64()
         bud = _budgets(max_bytes, n)
         at = _offsets(offsets, n)

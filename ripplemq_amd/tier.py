@@ -18,7 +18,9 @@ The engine's replica rings keep a retained window only (FORMAT.md §4): a fetch 
   offset (``p<pidx>/<first offset>.seg``), rolled at ``segment_file_bytes``. With
   ``DurableLog(spill_bytes=N)`` the spill keeps one buffer of ``N`` bytes and reads in passes of
   byte-budgeted fetches (``rmq_fetch_bytes``) instead of growing a buffer to whatever the
-  partitions hold.
+  partitions hold; with ``fill=True`` too, each pass is one filling fetch (``RMQ_FETCH_FILL``)
+  that serves the partitions in turn until the buffer is full, which a skewed backlog needs far
+  fewer of than equal shares.
 * ``DurableLog.read(p, off, max)`` serves ``[off, min(off + max, durable end))`` from the files
   (the broker's ``process_batch_read`` falls back to it on ``RMQ_EOFFSET`` after a spill, so a
   consumer below the rings gets what the reference's list would give it).
@@ -310,13 +312,23 @@ class DurableLog:
 
     def __init__(self, engine, directory: str, partitions, cursor: int, *,
                  segment_file_bytes: int = 64 << 20, fsync: bool = False, start=None,
-                 spill_bytes: int | None = None):
+                 spill_bytes: int | None = None, fill: bool = False):
         # spill_bytes: spill through one buffer of at most that many bytes, never grown, in passes of
         # byte-budgeted fetches (rmq_fetch_bytes); None: one fetch into a buffer grown to fit
+        # fill (with spill_bytes): each pass is one filling fetch (RMQ_FETCH_FILL) of all partitions
+        # instead, the partitions served in turn until the buffer is full
         self.spill_bytes = None if spill_bytes is None else int(spill_bytes) & ~15
+        self.fill = bool(fill)
+        self.passes = 0        # fetches of the last bounded spill, and the bytes each one used
+        self.pass_bytes = []
         if spill_bytes is not None:
             if "max_bytes" not in inspect.signature(engine.fetch).parameters:
                 raise ValueError("spill_bytes needs an engine whose fetch takes byte budgets (max_bytes)")
+        if fill:
+            if spill_bytes is None:
+                raise ValueError("fill needs spill_bytes (the buffer the passes fill)")
+            if "fill" not in inspect.signature(engine.fetch).parameters:
+                raise ValueError("fill needs an engine whose fetch fills a bounded output (fill)")
         self.engine = engine
         self.dir = directory
         self.cursor = int(cursor)
@@ -408,7 +420,7 @@ class DurableLog:
         cons = np.full(len(pidx), self.cursor, np.uint32)
         mx = np.full(len(pidx), 0xFFFFFFFF, np.uint32)
         if self.spill_bytes is not None:
-            return self._spill_bounded(pidx, cons, mx, t0)
+            return (self._spill_fill if self.fill else self._spill_bounded)(pidx, cons, mx, t0)
         # one fetch into a reused buffer (page-locked when the engine offers it), grown when short
         while True:
             if self._buf is not None:
@@ -432,13 +444,16 @@ class DurableLog:
         self._save_state(pidx, t0, t1, t2)
         return moved
 
-    def _append_runs(self, pidx, res, buf, budgeted: bool = False) -> int:
+    def _append_runs(self, pidx, res, buf, budgeted: bool = False, filling: bool = False) -> int:
         """The served runs of one spill fetch into their segment files; returns the records written.
-        budgeted: rows answered RMQ_ENOSPC for their byte budget (count 0) are no errors."""
+        budgeted: rows answered RMQ_ENOSPC for their byte budget (count 0) are no errors; filling:
+        nor are rows answered RMQ_PENDING (count 0), nor the one that names a record's size."""
         status = res["status"].astype(np.int64)
         ok = status == A.RMQ_OK
-        if budgeted:
+        if budgeted or filling:
             ok |= (status == A.RMQ_ENOSPC) & (res["reserved"] > 0)
+        if filling:
+            ok |= status == A.RMQ_PENDING
         bad = np.flatnonzero(~ok)
         if len(bad):
             p, st = int(pidx[bad[0]]), int(status[bad[0]])
@@ -498,6 +513,7 @@ class DurableLog:
             self._buf = self.engine.host_empty(cap, np.uint8) if hasattr(self.engine, "host_empty") else np.zeros(cap, np.uint8)
         want = np.zeros(n, np.int64)  # the record size a partition asked for in the last pass
         moved, t_fetch, t_files = 0, 0.0, 0.0
+        self.passes, self.pass_bytes = 0, []
         while True:
             ta = time.perf_counter()
             # the asking partitions first, as many as fit; the others share the rest (a partition
@@ -516,6 +532,8 @@ class DurableLog:
                                                    max_bytes=np.maximum(bud, 16))
             if rc != A.RMQ_OK:
                 raise EngineError(rc, "spill: budgeted fetch")
+            self.passes += 1
+            self.pass_bytes.append(int(used))
             tb = time.perf_counter()
             m = self._append_runs(pidx, res, buf, budgeted=True)
             t_fetch, t_files = t_fetch + tb - ta, t_files + time.perf_counter() - tb
@@ -529,6 +547,53 @@ class DurableLog:
         if (want > cap).any():
             k = int(np.flatnonzero(want > cap)[0])
             raise EngineError(A.RMQ_ENOSPC, f"spill of partition {int(pidx[k])}: a record of {int(want[k])} bytes "
+                                            f"exceeds spill_bytes = {cap}")
+        return moved
+
+    def _spill_fill(self, pidx, cons, mx, t0) -> int:
+        """spill through one buffer of spill_bytes, in passes of one filling fetch each
+        (RMQ_FETCH_FILL): the partitions are served whole in request order until the buffer is full,
+        the one that crosses its end is cut at a record boundary and the rest are put off
+        (RMQ_PENDING, their cursors where they were). The next pass starts at the partition the last
+        one was cut at, so the order rotates and every partition gets its turn; the passes end when
+        one moves nothing and puts nothing off."""
+        n, cap = len(pidx), self.spill_bytes
+        if self._buf is None:
+            self._buf = self.engine.host_empty(cap, np.uint8) if hasattr(self.engine, "host_empty") else np.zeros(cap, np.uint8)
+        moved, t_fetch, t_files, first, big = 0, 0.0, 0.0, 0, None
+        self.passes, self.pass_bytes = 0, []
+        while True:
+            ta = time.perf_counter()
+            order = (np.arange(n) + first) % n
+            rc, res_o, buf, used = self.engine.fetch(pidx[order], cons[order], mx[order], out=self._buf, commit=True,
+                                                     replica=True, fill=True)
+            if rc != A.RMQ_OK:
+                raise EngineError(rc, "spill: filling fetch")
+            self.passes += 1
+            self.pass_bytes.append(int(used))
+            tb = time.perf_counter()
+            res = np.empty_like(res_o)
+            res[order] = res_o  # (the rows in local order, as _append_runs reads them)
+            m = self._append_runs(pidx, res, buf, filling=True)
+            t_fetch, t_files = t_fetch + tb - ta, t_files + time.perf_counter() - tb
+            moved += m
+            status = res_o["status"]
+            nospc = np.flatnonzero(status == A.RMQ_ENOSPC)
+            if len(nospc):  # a record that the whole buffer cannot hold: nothing after it can be served
+                big = (int(pidx[order[nospc[0]]]), int(res_o["reserved"][nospc[0]]))
+                break
+            off = np.flatnonzero(status == A.RMQ_PENDING)
+            if not m and not len(off):
+                break
+            if len(off):
+                # the request that crossed the end: the last one served before the first put off (if
+                # it was cut it goes on; if not, or if it got nothing, it costs the pass nothing)
+                served = np.flatnonzero(res_o["bytes"][:off[0]] > 0)
+                first = int(order[served[-1] if len(served) else off[0]])
+        # (what the passes wrote is durable and recorded before a record too large is reported)
+        self._save_state(pidx, t0, t0 + t_fetch, t0 + t_fetch + t_files)
+        if big is not None:
+            raise EngineError(A.RMQ_ENOSPC, f"spill of partition {big[0]}: a record of {big[1]} bytes "
                                             f"exceeds spill_bytes = {cap}")
         return moved
 
