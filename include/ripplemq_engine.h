@@ -450,6 +450,42 @@ int rmq_fetch_at(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offse
                  uint32_t n, uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* bytes_used);
 int rmq_fetch_at_async(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
                        uint32_t n, uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket);
+/* rmq_fetch_at / rmq_fetch_at_async with a per-record position table (FORMAT.md §7 "Record table";
+   added after ABI 11 without a version bump; a Kafka fetch response is indexable by record, a run of
+   record images is a chain of length words). Everything rmq_fetch_at takes, with the same meaning
+   (offsets / max_bytes nullable, every `mem` bit, every request flag), and the call is answered as
+   rmq_fetch_at answers it: rows, output bytes, bytes_used, commits and the position cache are the
+   same bit for bit. One device pass after the gather (and the verify) then looks at the final rows:
+   row r owns w_r = count_r + 1 table words if its status is RMQ_OK and count_r > 0, else none (empty
+   rows, RMQ_EOFFSET, error rows, both kinds of RMQ_ENOSPC, RMQ_PENDING, RMQ_ECORRUPT).
+   rec_row[r] = w_0 + ... + w_{r-1} for r in [0, n] (n + 1 words; rec_row[n] = the words the call
+   needs). For an owning row rec_pos[rec_row[r] + k], k in [0, count_r), is the byte position of its
+   record k inside its run out[out_pos_r, out_pos_r + bytes_r) (word 0 is 0), and
+   rec_pos[rec_row[r] + count_r] = bytes_r: word for word what rmq_scan_records writes as pos_out for
+   that run and what rmq_restore_item.table_start points at. A row's words are written only if
+   rec_row[r] + w_r <= rec_cap; other words of rec_pos are left as they were. rec_row[n] > rec_cap
+   returns RMQ_ENOSPC (from the call or the poll), with RMQ_FETCH_FILL too: the one way a filling
+   call returns it; the caller tells the overflows apart by bytes_used > out_cap versus
+   rec_row[n] > rec_cap. rec_cap >= out_cap / 16 + n always suffices (a record is at least 16
+   bytes). rec_row == NULL, rec_pos == NULL, rec_cap == 0 is exactly rmq_fetch_at; rec_pos == NULL
+   needs rec_cap == 0 and is a size probe (rec_row is written); rec_row == NULL with anything else,
+   or rec_pos == NULL with rec_cap != 0, is RMQ_EINVAL. Both arrays have the memory kind of `out`
+   (mem & 3): RMQ_MEM_HOST: ordinary host arrays, valid until the ticket completes, staged in slot
+   scratch and copied back with the output bytes; RMQ_MEM_DEVICE: device memory, 8-byte aligned
+   (RMQ_EINVAL otherwise), written in place. The words come from length words that nothing has
+   checked unless the request carries RMQ_FETCH_VERIFY (a refused request owns no words): on an
+   intact log they are the true record starts; on a damaged length word of an unflagged request they
+   are still bounded: every word a multiple of 16 in [0, bytes_r], word 0 = 0, word count_r =
+   bytes_r (q_0 = 0, q_{k+1} = min(q_k + 16 + align16(len at q_k), bytes_r) in 64-bit; once a q_k
+   reaches bytes_r the words left are bytes_r), no byte outside the run is read and no word outside
+   the row's own is written. A call with a table is never held back to go with later asynchronous
+   fetches; rmq_fetch_poll completes these tickets too. */
+int rmq_fetch_table(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
+                    uint32_t n, uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res,
+                    uint64_t* rec_row, uint64_t* rec_pos, uint64_t rec_cap, uint64_t* bytes_used);
+int rmq_fetch_table_async(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
+                          uint32_t n, uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res,
+                          uint64_t* rec_row, uint64_t* rec_pos, uint64_t rec_cap, uint64_t* ticket);
 
 /* ---- replication transport (FORMAT.md §9) ---- */
 /* 128-byte communicator id: one rank creates it, the application hands it to every rank. */
@@ -736,7 +772,9 @@ int rmq_host_unregister(rmq_engine* e, void* p);
    (the exchanges and the host's waits between them included), launches = calls. 7: rmq_restore, an
    event before its first kernel to one after its last (the staging copies before them outside),
    launches = calls. 8: rmq_reindex, an event before its first plan to one after its last kernel,
-   launches = calls. */
+   launches = calls. 9: the record-table kernels of rmq_fetch_table, an event before the first to one
+   after the last, launches = calls (such a fetch runs once, without dispatch spans, as a budgeted
+   one; its table kernels lie inside its region 4 too). */
 int rmq_profile_enable(rmq_engine* e, int enable);
 int rmq_profile_query(rmq_engine* e, int kernel, uint64_t* launches, double* total_ms);
 /* Device name / CU count for reports. */

@@ -191,6 +191,8 @@ _SIGS = {
     "rmq_fetch_bytes_async": (C.c_int, [vp, vp, vp, u32, u32, vp, u64, vp, C.POINTER(u64)]),
     "rmq_fetch_at": (C.c_int, [vp, vp, vp, vp, u32, u32, vp, u64, vp, C.POINTER(u64)]),
     "rmq_fetch_at_async": (C.c_int, [vp, vp, vp, vp, u32, u32, vp, u64, vp, C.POINTER(u64)]),
+    "rmq_fetch_table": (C.c_int, [vp, vp, vp, vp, u32, u32, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]),
+    "rmq_fetch_table_async": (C.c_int, [vp, vp, vp, vp, u32, u32, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]),
     "rmq_get_partition_state": (C.c_int, [vp, u32, C.POINTER(RmqPartitionState)]),
     "rmq_get_partition_states": (C.c_int, [vp, u32, u32, vp]),
     "rmq_read_segment": (C.c_int, [vp, u32, u32, u64, u64, vp]),

@@ -590,7 +590,8 @@ void free_engine(rmq_engine* e) {
   repair_remote_free(e);
   if (e->state_stage) hipHostFree(e->state_stage);
   for (rmq_engine::FetchSlot& f : e->fslot) {
-    void* fs[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_out, f.d_bud, f.d_at, f.d_csum_fill};
+    void* fs[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_out, f.d_bud, f.d_at, f.d_csum_fill,
+                  f.d_tsum, f.d_trow, f.d_tpos};
     for (void* p : fs) bufs.push_back(p);
     if (f.h_bud) hipHostFree(f.h_bud);
     if (f.h_at) hipHostFree(f.h_at);
@@ -891,11 +892,14 @@ int rmq_create(const rmq_config* cfg, rmq_engine** out) {
   }
   if (e->stamps_path) CREATE_TRY(dalloc(&e->d_stamps, (size_t)(2u * e->cu_count + kMaxTiles + (P + kPipeThreads - 1) / kPipeThreads +
                                                        kMaxTiles * kTileRecs / (kTaskRecs * kPipeThreads / 64)) * 64));
-  CREATE_HIP(hipHostMalloc((void**)&e->fetch_need_host, 8 * rmq_engine::kFetchSlots, hipHostMallocCoherent | hipHostMallocMapped));
+  CREATE_HIP(hipHostMalloc((void**)&e->fetch_need_host, 16 * rmq_engine::kFetchSlots, hipHostMallocCoherent | hipHostMallocMapped));
   for (uint32_t k = 0; k < rmq_engine::kFetchSlots; ++k) {
     e->fslot[k].need = e->fetch_need_host + k;
     *e->fslot[k].need = 0;
     CREATE_HIP(hipHostGetDevicePointer((void**)&e->fslot[k].need_dev, e->fslot[k].need, 0));
+    e->fslot[k].tneed = e->fetch_need_host + rmq_engine::kFetchSlots + k;
+    *e->fslot[k].tneed = 0;
+    CREATE_HIP(hipHostGetDevicePointer((void**)&e->fslot[k].tneed_dev, e->fslot[k].tneed, 0));
   }
   CREATE_HIP(hipHostMalloc((void**)&e->done_host, 64, hipHostMallocCoherent | hipHostMallocMapped));
   e->done_host[0] = e->done_host[1] = 0;
@@ -1621,7 +1625,7 @@ int fetch_alloc(void** p, size_t bytes) {
 
 int fetch_slot_reserve(rmq_engine::FetchSlot& f, uint32_t n, uint64_t stage, hipStream_t s) {
   if (n > f.cap) {
-    void* ds[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_bud, f.d_at, f.d_csum_fill};
+    void* ds[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_bud, f.d_at, f.d_csum_fill, f.d_tsum, f.d_trow};
     for (void* p : ds)
       if (p) hipFree(p);
     if (f.h_req) hipHostFree(f.h_req);
@@ -1629,7 +1633,7 @@ int fetch_slot_reserve(rmq_engine::FetchSlot& f, uint32_t n, uint64_t stage, hip
     if (f.h_bud) hipHostFree(f.h_bud);
     if (f.h_at) hipHostFree(f.h_at);
     f.d_req = f.d_cpre = f.h_req = f.h_bud = f.d_bud = nullptr;
-    f.d_res = f.d_aux = f.d_csum = f.h_res = f.h_at = f.d_at = f.d_csum_fill = nullptr;
+    f.d_res = f.d_aux = f.d_csum = f.h_res = f.h_at = f.d_at = f.d_csum_fill = f.d_tsum = f.d_trow = nullptr;
     f.cap = 0;
     const uint32_t cap = std::max<uint32_t>(n, 1024);
     int rc = fetch_alloc((void**)&f.d_req, (size_t)cap * 16);
@@ -1686,12 +1690,27 @@ int fetch_slot_step(rmq_engine* e, rmq_engine::FetchSlot& f, bool wait, uint64_t
     // some request did not fit iff the bytes needed exceed the output (requests are placed in
     // order: the one holding byte out_cap is cut), so no pass over the rows
     f.rc = __atomic_load_n(f.need, __ATOMIC_ACQUIRE) > f.out_cap ? RMQ_ENOSPC : RMQ_OK;
+    // (a table that needs more words than rec_cap: the same code, told apart by rec_row[n] > rec_cap)
+    if (f.table && __atomic_load_n(f.tneed, __ATOMIC_ACQUIRE) > f.t_cap) f.rc = RMQ_ENOSPC;
     f.phase = 2;
-    if (f.mem == RMQ_MEM_HOST && f.out_cap) {
+    if (f.mem == RMQ_MEM_HOST && (f.out_cap || f.t_row)) {
+      if (f.t_row) {
+        // a host table: rec_row whole, and of rec_pos the words the walk wrote: rows fit while
+        // their prefix does (the prefix rises with r), so those are the words before the first row
+        // that does not; the others stay untouched in the caller's array, as on the device
+        uint64_t words = 0;
+        for (uint32_t r = 0; r < f.n; ++r) {
+          const uint64_t w = f.res[r].status == RMQ_OK && f.res[r].count ? (uint64_t)f.res[r].count + 1 : 0;
+          if (w > f.t_cap - words) break;
+          words += w;
+        }
+        HIP_TRY(hipMemcpyAsync(f.t_row, f.d_trow, ((size_t)f.n + 1) * 8, hipMemcpyDeviceToHost, e->fetch_out_s));
+        if (words) HIP_TRY(hipMemcpyAsync(f.t_pos, f.d_tpos, (size_t)words * 8, hipMemcpyDeviceToHost, e->fetch_out_s));
+      }
       // copy back the byte runs of the served requests only: the regions of requests that did not
       // fit stay untouched in the caller's buffer, as with a device buffer the gather writes itself
       uint64_t lo = 0, hi = 0;
-      for (uint32_t r = 0; r <= f.n; ++r) {
+      for (uint32_t r = 0; f.out_cap && r <= f.n; ++r) {
         const bool served = r < f.n && f.res[r].status == RMQ_OK && f.res[r].bytes;
         if (served && f.res[r].out_pos == hi && hi > lo) {
           hi += f.res[r].bytes;
@@ -1728,10 +1747,17 @@ namespace {
 // Issue a fetch into the next slot: its kernels on the pipeline stream, an event after them.
 // max_bytes: the requests' byte budgets (rmq_fetch_bytes, FORMAT.md §7), or null: none.
 // offsets: the requests' explicit offsets (rmq_fetch_at, FORMAT.md §7), or null: none.
+// rec_row, rec_pos, rec_cap: the record table (rmq_fetch_table, FORMAT.md §7), or null, null, 0: none.
 int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
                 uint32_t n, uint32_t mem,
-                uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket, bool sync) {
+                uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket, bool sync,
+                uint64_t* rec_row = nullptr, uint64_t* rec_pos = nullptr, uint64_t rec_cap = 0) {
   if (!e || !ticket) return RMQ_EINVAL;
+  const bool table = rec_row != nullptr;
+  if (!rec_row && (rec_pos || rec_cap)) return RMQ_EINVAL;
+  if (!rec_pos && rec_cap) return RMQ_EINVAL;  // (rec_pos null with rec_cap 0: a size probe)
+  if ((mem & 3u) == RMQ_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(rec_row) | reinterpret_cast<uintptr_t>(rec_pos)) & 7u))
+    return RMQ_EINVAL;
   bool rows_pinned = (mem & RMQ_FETCH_PINNED_ROWS) != 0;
   const bool rows_dev = (mem & RMQ_FETCH_DEVICE_ROWS) != 0;
   const bool fill = (mem & RMQ_FETCH_FILL) != 0;  // (FORMAT.md §7 "Filling a bounded output")
@@ -1800,6 +1826,8 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offset
   }
   const uint64_t tk = ++e->fetch_seq;
   if (!n) {  // nothing to fetch: complete at once
+    if (table && mem == RMQ_MEM_HOST) rec_row[0] = 0;  // (rec_row has n + 1 words)
+    if (table && mem == RMQ_MEM_DEVICE) HIP_TRY(hipMemset(rec_row, 0, 8));
     e->fetch_done.push_back({tk, (uint64_t)(int64_t)RMQ_OK, 0});
     while (e->fetch_done.size() > 256) e->fetch_done.pop_front();
     *ticket = tk;
@@ -1876,6 +1904,31 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offset
     rc = fetch_alloc((void**)&f.d_csum_fill, (size_t)f.csum_lines * kCsumStride * 8);
     if (rc) return rc;
   }
+  // (the record table's chunk words, and the device staging of a host table: made by the slot's
+  // first table call, or its first with host arrays; the staged rec_pos grows as the staged output)
+  uint64_t* d_trow = rec_row;
+  uint64_t* d_tpos = rec_pos;
+  if (table && !f.d_tsum) {
+    rc = fetch_alloc((void**)&f.d_tsum, (size_t)f.csum_lines * 8);
+    if (rc) return rc;
+  }
+  if (table && mem == RMQ_MEM_HOST) {
+    if (!f.d_trow) {
+      rc = fetch_alloc((void**)&f.d_trow, ((size_t)f.cap + 1) * 8);
+      if (rc) return rc;
+    }
+    if (rec_cap > f.tpos_alloc) {
+      if (f.d_tpos) hipFree(f.d_tpos);
+      f.d_tpos = nullptr;
+      f.tpos_alloc = 0;
+      if (rec_cap > (1ull << 60)) return RMQ_ENOMEM;
+      rc = fetch_alloc((void**)&f.d_tpos, (size_t)rec_cap * 8);
+      if (rc) return rc;
+      f.tpos_alloc = rec_cap;
+    }
+    d_trow = f.d_trow;
+    d_tpos = rec_pos ? f.d_tpos : nullptr;
+  }
   if (dma_in) {
     HIP_TRY(hipMemcpyAsync(f.d_req, rows_pinned ? static_cast<const void*>(reqs) : static_cast<const void*>(f.h_req),
                            (size_t)n * sizeof(rmq_fetch_req), hipMemcpyHostToDevice, e->copy_s));
@@ -1897,8 +1950,9 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offset
     // whose entries are all RMQ_OFFSET_NONE is read by nothing and launches the plain resolve, but
     // the call is still not held: FORMAT.md §7 says so of every call with offsets != NULL)
     // (nor one that fills its output: its fill kernel runs before its own gather)
+    // (nor one with a record table: its table kernels follow its own gather and verify)
     const bool hold =
-        !sync && !any && !verify && !d_bud && !offsets && !fill && !dma && !e->profile && e->fetch_coalesce > 1;
+        !sync && !any && !verify && !d_bud && !offsets && !fill && !table && !dma && !e->profile && e->fetch_coalesce > 1;
     if (!hold) {
       rc = fetch_flush(e);
       if (rc) return rc;
@@ -1942,11 +1996,12 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offset
     // (profiling replays a fetch's kernels back to back; a committing fetch runs once: each run
     // would commit again and the next would read from the committed offset)
     // (nor is a verifying one replayed: its third kernel rewrites the rows the gather wrote)
-    // (nor a budgeted one: its three kernels are launched without dispatch spans; nor a filling one)
-    const uint32_t runs = hold ? 0u : e->profile && !any && !verify && !d_bud && !fill ? e->fetch_replay : 1u;
+    // (nor a budgeted one: its three kernels are launched without dispatch spans; nor a filling one;
+    // nor one with a record table: its rows feed the table kernels once)
+    const uint32_t runs = hold ? 0u : e->profile && !any && !verify && !d_bud && !fill && !table ? e->fetch_replay : 1u;
     // (a committing fetch records no dispatch spans: the events the kernels' own dispatches record
     // were measured to hold the second kernel ~10 us behind the first, which its one run would carry)
-    const bool spans = e->profile && !any && !verify && !d_bud && !fill;
+    const bool spans = e->profile && !any && !verify && !d_bud && !fill && !table;
     if (e->profile) {  // kernel 3: the first run's dispatch spans; 4: every run
       if (spans) {
         for (hipEvent_t& x : ev) x = pool_event(e);
@@ -2001,6 +2056,27 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offset
       launch_fetch_verify(v, audit_wgs(e), e->main_s);
       HIP_TRY(hipGetLastError());
     }
+    if (table) {  // the record table from the final rows (kernel 9: the span of its kernels)
+      FetchTableArgs t{};
+      t.rows = a.res_host;
+      t.out = d_out;
+      t.rec_row = d_trow;
+      t.rec_pos = d_tpos;
+      t.rec_cap = rec_cap;
+      t.tsum = f.d_tsum;
+      t.need_host = f.tneed_dev;
+      t.n = n;
+      hipEvent_t t0 = nullptr, t1 = nullptr;
+      if (e->profile) {
+        t0 = pool_event(e);
+        t1 = pool_event(e);
+        e->prof[9].push_back({t0, t1});
+        HIP_TRY(hipEventRecord(t0, e->main_s));
+      }
+      launch_fetch_table(t, audit_wgs(e), e->main_s);
+      HIP_TRY(hipGetLastError());
+      if (e->profile) HIP_TRY(hipEventRecord(t1, e->main_s));
+    }
     if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
     if (hold) {
       // (the completion event: recorded when fetch_flush launches the kernels)
@@ -2022,6 +2098,10 @@ int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offset
   f.out = out;
   f.out_cap = out_cap;
   f.res = res;
+  f.table = table;
+  f.t_row = table && mem == RMQ_MEM_HOST ? rec_row : nullptr;
+  f.t_pos = rec_pos;
+  f.t_cap = rec_cap;
   e->fslot_next = (e->fslot_next + 1) % rmq_engine::kFetchSlots;
   while (e->fetch_done.size() > 256) e->fetch_done.pop_front();
   *ticket = tk;
@@ -2093,6 +2173,24 @@ int rmq_fetch_at(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offse
   if (!n) return RMQ_OK;
   uint64_t t = 0;
   const int rc = fetch_issue(e, reqs, offsets, max_bytes, n, mem, out, out_cap, res, &t, true);
+  if (rc) return rc;
+  return rmq_fetch_poll(e, t, 1, bytes_used);
+}
+
+int rmq_fetch_table_async(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
+                          uint32_t n, uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res,
+                          uint64_t* rec_row, uint64_t* rec_pos, uint64_t rec_cap, uint64_t* ticket) {
+  return fetch_issue(e, reqs, offsets, max_bytes, n, mem, out, out_cap, res, ticket, false, rec_row, rec_pos, rec_cap);
+}
+
+int rmq_fetch_table(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
+                    uint32_t n, uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res,
+                    uint64_t* rec_row, uint64_t* rec_pos, uint64_t rec_cap, uint64_t* bytes_used) {
+  if (bytes_used) *bytes_used = 0;
+  if (!e) return RMQ_EINVAL;
+  if (!n && !rec_row && !rec_pos && !rec_cap) return RMQ_OK;  // (exactly rmq_fetch_at)
+  uint64_t t = 0;
+  const int rc = fetch_issue(e, reqs, offsets, max_bytes, n, mem, out, out_cap, res, &t, true, rec_row, rec_pos, rec_cap);
   if (rc) return rc;
   return rmq_fetch_poll(e, t, 1, bytes_used);
 }
@@ -2346,7 +2444,7 @@ int rmq_profile_enable(rmq_engine* e, int enable) {
 }
 
 int rmq_profile_query(rmq_engine* e, int kernel, uint64_t* launches, double* total_ms) {
-  if (!e || kernel < 0 || kernel > 8) return RMQ_EINVAL;
+  if (!e || kernel < 0 || kernel > 9) return RMQ_EINVAL;
   EngineLock g(e);
   HIP_TRY(hipSetDevice(e->device));
   int rc = settle(e);

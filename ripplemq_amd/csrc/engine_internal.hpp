@@ -356,6 +356,11 @@ struct rmq_engine {
     uint64_t* h_at = nullptr;    // pinned [cap] explicit offsets of host rows (rmq_fetch_at), copied at the call;
                                  //   made by the slot's first call that passes offsets (as d_at)
     uint64_t* d_at = nullptr;    // [cap] their device copy where RMQ_FETCH_DMA moves the request rows
+    // record table (rmq_fetch_table), made by the slot's first table call (as d_at and d_csum_fill)
+    uint64_t* d_tsum = nullptr;  // csum_lines words: the table words of each chunk of rows
+    uint64_t* d_trow = nullptr;  // [cap + 1] device staging of a host rec_row
+    uint64_t* d_tpos = nullptr;  // [tpos_alloc] device staging of a host rec_pos (grows as d_out does)
+    uint64_t tpos_alloc = 0;
     uint32_t cap = 0;
     uint8_t* d_out = nullptr;    // device staging of a host output
     uint64_t out_alloc = 0;
@@ -366,6 +371,8 @@ struct rmq_engine {
     bool rows_pinned = false;      // the caller's rows read / written in place (pinned or device rows)
     uint64_t* need = nullptr;      // bytes needed: a word of fetch_need_host (the gather stores it)
     uint64_t* need_dev = nullptr;  // its device address
+    uint64_t* tneed = nullptr;     // table words needed (rec_row[n]): the slot's second word of fetch_need_host
+    uint64_t* tneed_dev = nullptr;
     // the fetch in flight: ticket 0 = idle; phase 1: kernels, 2: host output copies
     uint64_t ticket = 0;
     int phase = 0;
@@ -374,13 +381,17 @@ struct rmq_engine {
     uint8_t* out = nullptr;
     uint64_t out_cap = 0;
     rmq_fetch_res* res = nullptr;
+    bool table = false;            // a ticket with a record table: rec_row[n] > t_cap completes RMQ_ENOSPC
+    uint64_t* t_row = nullptr;     //   a host table's arrays (copied back with the host output), else null
+    uint64_t* t_pos = nullptr;
+    uint64_t t_cap = 0;
     bool pending = false;  // its kernels held back to go with the next asynchronous fetches (fetch_flush)
     FetchArgs args{};      //   and their arguments
   };
   static constexpr uint32_t kFetchSlots = 4;
   FetchSlot fslot[kFetchSlots];
   uint32_t fslot_next = 0;
-  uint64_t* fetch_need_host = nullptr;  // [kFetchSlots] coherent pinned words (FetchSlot::need)
+  uint64_t* fetch_need_host = nullptr;  // [2][kFetchSlots] coherent pinned words (FetchSlot::need, then ::tneed)
   uint64_t fetch_seq = 0;        // tickets
   std::vector<uint32_t> fetch_stamp;  // RMQ_FETCH_COMMIT duplicate check ([P][C] generation stamps)
   std::vector<uint32_t> fetch_stamp_rep;  // the same for replica reads ([P]: one replica cursor each)
@@ -416,14 +427,14 @@ struct rmq_engine {
   uint32_t ctl_cap = 0;
   // profiling: pipeline launches are timed as one region (event before the first launch after
   // enable, event at the next drain) so no per-launch events sit between kernels; fetch kernels
-  // keep per-launch event pairs (prof[3], prof[4]), and so do every rmq_scrub (prof[2]), every rmq_repair (prof[5]), every rmq_repair_remote (prof[6]), every rmq_restore (prof[7]) and every rmq_reindex (prof[8])
+  // keep per-launch event pairs (prof[3], prof[4]), and so do every rmq_scrub (prof[2]), every rmq_repair (prof[5]), every rmq_repair_remote (prof[6]), every rmq_restore (prof[7]), every rmq_reindex (prof[8]) and every fetch's record-table kernels (prof[9])
   uint32_t profile = 0;
   uint32_t fetch_replay = 1;     // rmq_profile_enable(k >= 2): each fetch's kernels run k times
   uint64_t prof_fetch_runs = 0;
   uint64_t prof_launches = 0, prof_batches = 0;
   hipEvent_t prof_t0 = nullptr, prof_t1 = nullptr;
   bool prof_started = false, prof_ended = false;
-  std::vector<EvPair> prof[9];
+  std::vector<EvPair> prof[10];
   // rmq_scrub, rmq_repair, rmq_repair_remote, rmq_reindex (audit.cpp): device buffers of one call's
   // range of n partitions, grown on demand (a capacity in elements next to each)
   struct Audit {

@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "device_common.hpp"
+#include "fetch_table_walk.hpp"
 #include "kernels.hpp"
 
 namespace rmq {
@@ -875,6 +876,120 @@ void launch_fetch_verify(const FetchVerifyArgs& a, uint32_t max_wgs, hipStream_t
   hipLaunchKernelGGL(fetch_verify_kernel, dim3(wgs), dim3(kVT), 0, s, a);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Record table (rmq_fetch_table, FORMAT.md §7 "Record table"): the kernels after the gather (and
+// the verify) of a ticket that asks for one
+// ---------------------------------------------------------------------------------------------
+constexpr u32 kTW = 256;  // threads per table-walk workgroup: a wave per request
+
+// The words row r owns, from its final words {count | bytes << 32, status}: count + 1 if it is
+// served RMQ_OK with records, else none.
+__device__ __forceinline__ u64 table_words(u64 w2, u64 w3) { return (int)(u32)w3 == kOk && (u32)w2 ? (u64)(u32)w2 + 1ull : 0ull; }
+
+// Scan, first half: a workgroup per chunk of kFetchChunk rows, a thread per row: each row's words
+// into rec_row[r] (the second half turns them into their prefix in place), the chunk's into tsum.
+__global__ __launch_bounds__(kFetchChunk) void fetch_table_sum_kernel(FetchTableArgs a) {
+  const u32 c = blockIdx.x, tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
+  __shared__ u64 s_sum[kFetchChunk / 64];
+  const u32 r = c * kFetchChunk + tid;
+  u64 tw = 0;
+  if (r < a.n) {
+    const ulonglong2 hi = *reinterpret_cast<const ulonglong2*>(a.rows + 4ull * r + 2);
+    tw = table_words(hi.x, hi.y);
+    a.rec_row[r] = tw;
+  }
+  const u64 inc = wave_incl_scan(tw);
+  if (lane == 63) s_sum[w] = inc;
+  __syncthreads();
+  if (tid == 0) a.tsum[c] = s_sum[0] + s_sum[1] + s_sum[2] + s_sum[3];
+}
+
+// Scan, second half: the same grid; the words before the chunk from the chunk sums (every wave on
+// its own, as the fill kernel reads its sums), an exclusive scan of the chunk's rows, rec_row[r]
+// rewritten in place by the thread that read it; the last row's thread adds rec_row[n] and tells the
+// host. Sums of integers in a fixed order: the same table from the same rows, run after run.
+__global__ __launch_bounds__(kFetchChunk) void fetch_table_rows_kernel(FetchTableArgs a) {
+  static_assert(kFetchChunk == 256, "four waves, a thread per row of the chunk");
+  const u32 c = blockIdx.x, tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
+  __shared__ u64 s_sum[kFetchChunk / 64];
+  u64 base = 0;
+  for (u32 k = lane; k < c; k += 64) base += a.tsum[k];
+  base = bcast_u64(wave_incl_scan(base), 63);
+  const u32 r = c * kFetchChunk + tid;
+  const u64 tw = r < a.n ? a.rec_row[r] : 0ull;
+  const u64 inc = wave_incl_scan(tw);
+  if (lane == 63) s_sum[w] = inc;
+  __syncthreads();
+  u64 P = base + inc - tw;
+  for (u32 k = 0; k < w; ++k) P += s_sum[k];
+  if (r < a.n) a.rec_row[r] = P;
+  if (r + 1 == a.n) {
+    a.rec_row[a.n] = P + tw;
+    __hip_atomic_store(a.need_host, P + tw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+// The table of one run (wave-uniform arguments): the nb16 pieces at base hold `count` records;
+// words[k], k < count, gets the byte position of record k and words[count] the run's bytes. The
+// walk is verify_slice's: the length words read as windows of 64 pieces, the next window in flight
+// while one is walked, lane j keeping the start of record done + j, then one 8-byte store per lane
+// for the round's (at most 64) records. Nothing here trusts a length word: slice_lens loads no piece
+// at or beyond nb16, table_next never steps past nb16, and a walk that reaches nb16 before `count`
+// records (a damaged length word) ends there with the words left set to the run's bytes. Exactly
+// the words [0, count] are written.
+__device__ __forceinline__ void table_walk(const uint8_t* base, u32 nb16, u32 count, u64* words) {
+  const u32 lane = lane_id();
+  // piece of the next record start; records placed; window (all wave-uniform, and 32-bit: a row's
+  // bytes are a 32-bit word, so nb16 < 2^28 and table_next<u32> cannot wrap)
+  u32 q = 0, done = 0, wk = 0;
+  u32 W0 = slice_lens(base, nb16, 0, lane), W1 = slice_lens(base, nb16, 1, lane);
+  while (done < count && q < nb16) {
+    u32 myq = 0, nrec = 0;
+    const u32 lim = count - done < 64u ? count - done : 64u;
+    while (nrec < lim && q < nb16) {
+      const u32 k = q >> 6;
+      if (k != wk) {
+        W0 = k == wk + 1u ? W1 : slice_lens(base, nb16, k, lane);
+        W1 = slice_lens(base, nb16, (u64)k + 1ull, lane);
+        wk = k;
+      }
+      const u32 Lq = (u32)__builtin_amdgcn_readlane((int)W0, __builtin_amdgcn_readfirstlane((int)(q & 63u)));
+      myq = lane == nrec ? q : myq;
+      q = table_next<u32>(q, Lq, nb16);
+      ++nrec;
+    }
+    if (lane < nrec) words[(u64)done + lane] = 16ull * myq;
+    done += nrec;
+  }
+  for (u64 k = (u64)done + lane; k <= count; k += 64) words[k] = 16ull * nb16;  // the end word (and an early end's rest)
+}
+
+// A wave per request, the waves striding over the requests on a bounded grid (the verify kernel's
+// shape): a row that owns words, all of them inside rec_cap, has its run walked.
+__global__ __launch_bounds__(kTW) void fetch_table_walk_kernel(FetchTableArgs a) {
+  const u32 stride = gridDim.x * (kTW / 64);
+  for (u32 r = (u32)__builtin_amdgcn_readfirstlane(blockIdx.x * (kTW / 64) + (threadIdx.x >> 6)); r < a.n; r += stride) {
+    const ulonglong2 lo = *reinterpret_cast<const ulonglong2*>(a.rows + 4ull * r);
+    const ulonglong2 hi = *reinterpret_cast<const ulonglong2*>(a.rows + 4ull * r + 2);
+    const u64 w1 = bcast_u64(lo.y, 0), w2 = bcast_u64(hi.x, 0), w3 = bcast_u64(hi.y, 0);
+    const u64 tw = table_words(w2, w3);
+    if (!tw) continue;
+    const u64 t0 = bcast_u64(a.rec_row[r], 0);
+    if (t0 > a.rec_cap || tw > a.rec_cap - t0) continue;  // its words do not fit: none of them written
+    table_walk(a.out + w1, (u32)(w2 >> 36), (u32)w2, a.rec_pos + t0);
+  }
+}
+
+void launch_fetch_table(const FetchTableArgs& a, uint32_t max_wgs, hipStream_t s) {
+  if (!a.n) return;
+  const dim3 chunks((a.n + kFetchChunk - 1) / kFetchChunk);
+  hipLaunchKernelGGL(fetch_table_sum_kernel, chunks, dim3(kFetchChunk), 0, s, a);
+  hipLaunchKernelGGL(fetch_table_rows_kernel, chunks, dim3(kFetchChunk), 0, s, a);
+  if (!a.rec_cap) return;  // a size probe
+  const uint32_t wgs = std::min<uint32_t>((a.n + kTW / 64 - 1) / (kTW / 64), std::max<uint32_t>(max_wgs, 1u));
+  hipLaunchKernelGGL(fetch_table_walk_kernel, dim3(wgs), dim3(kTW), 0, s, a);
+}
+
 // ev[4]: start / end events of the two kernels, recorded by the dispatches themselves
 // (profiling: kernel time without the host's launch gaps), or null
 // Load the fetch kernels' code at engine creation (a process's first launch of a kernel otherwise
@@ -888,6 +1003,9 @@ void preload_fetch_kernels() {
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_trim_kernel));
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_resolve_kernel<false, true>));
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_fill_kernel));
+  (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_table_sum_kernel));
+  (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_table_rows_kernel));
+  (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_table_walk_kernel));
 }
 
 static void launch_batch(const FetchBatch& b, hipStream_t s, const hipEvent_t* e) {

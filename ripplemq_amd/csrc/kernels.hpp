@@ -384,6 +384,21 @@ struct FetchFillArgs {
   uint32_t verify;           // the host checked RMQ_FETCH_VERIFY requests in the call (else flags ignored)
   uint32_t pad;
 };
+// The kernels after the gather (and the verify) of a ticket with a record table (rmq_fetch_table,
+// FORMAT.md §7 "Record table"; their own arguments, as the verify kernel's): from the final rows,
+// the words each row owns, their exclusive prefix into rec_row, and every owning row's record
+// starts, walked from the length words of its run in the output, into rec_pos.
+struct FetchTableArgs {
+  const uint64_t* rows;      // [n][4] the final result rows (FetchArgs::res_host)
+  const uint8_t* out;        // the device output (the caller's, or the slot's staging of a host output)
+  uint64_t* rec_row;         // [n + 1] device memory: the caller's, or the slot's staging of host arrays
+  uint64_t* rec_pos;         // [rec_cap], or null with rec_cap 0 (a size probe: no walk)
+  uint64_t rec_cap;
+  uint64_t* tsum;            // [chunks of n] words owned by each chunk of kFetchChunk rows (scratch)
+  uint64_t* need_host;       // host-visible word (coherent pinned): rec_row[n], the words the call needs
+  uint32_t n;
+  uint32_t pad;
+};
 
 
 struct ConsumerCommitArgs {  // one item per (partition, consumer): the host resolved last-writer-wins
@@ -613,6 +628,7 @@ void launch_fetch_budget(const FetchArgs& a, const FetchTrimArgs& t, hipStream_t
 // (a.csum is what the resolve adds into; the gather reads f.csum_out).
 void launch_fetch_fill(const FetchArgs& a, const FetchFillArgs& f, hipStream_t s);
 void launch_fetch_verify(const FetchVerifyArgs& a, uint32_t max_wgs, hipStream_t s);  // after the ticket's gather
+void launch_fetch_table(const FetchTableArgs& a, uint32_t max_wgs, hipStream_t s);  // after the gather and the verify
 void preload_fetch_kernels();
 
 void launch_consumer_commit(const ConsumerCommitArgs& a, hipStream_t s);

@@ -57,6 +57,17 @@ def _offsets(offsets, n: int) -> np.ndarray | None:
     return np.ascontiguousarray(np.broadcast_to(np.asarray(offsets, np.uint64), (n,)), np.uint64)
 
 
+def _host_table(table, n: int, out_cap: int):
+    """(rec_row, rec_pos, rec_cap) of a host record table (rmq_fetch_table): True: fresh arrays of the
+    size that always suffices, out_cap / 16 + n words; or the caller's (rec_row, rec_pos[, rec_cap])
+    uint64 arrays, rec_pos None: the size probe."""
+    if table is True:
+        cap = int(out_cap) // 16 + n
+        return np.zeros(n + 1, np.uint64), np.zeros(max(cap, 1), np.uint64), cap
+    row, pos = table[0], table[1]
+    return row, pos, int(table[2]) if len(table) > 2 else (0 if pos is None else pos.size)
+
+
 def _ptr_reused(a: np.ndarray) -> int:
     """_ptr of an array passed again and again (a fetch's request and result rows, views of
     page-locked memory from fetch_rows): numpy's .ctypes.data costs ~1.5 us a call, a checked cache
@@ -150,10 +161,10 @@ def state_to_dict(s: A.RmqPartitionState, rf: int) -> dict:
 
 class FetchTicket:
     """An rmq_fetch_async in flight: its ticket and the arrays the engine writes into."""
-    __slots__ = ("ticket", "req", "res", "out")
+    __slots__ = ("ticket", "req", "res", "out", "table")
 
-    def __init__(self, ticket: int, req: np.ndarray, res: np.ndarray, out: np.ndarray | None):
-        self.ticket, self.req, self.res, self.out = ticket, req, res, out
+    def __init__(self, ticket: int, req: np.ndarray, res: np.ndarray, out: np.ndarray | None, table=None):
+        self.ticket, self.req, self.res, self.out, self.table = ticket, req, res, out, table
 
 
 class Engine:
@@ -422,7 +433,7 @@ class Engine:
 
     def fetch(self, pidx, consumer, max_records, out_cap: int | None = None, commit: bool = False,
               out: np.ndarray | None = None, replica: bool = False, verify: bool = False, max_bytes=None,
-              offsets=None, fill: bool = False):
+              offsets=None, fill: bool = False, table=None):
         """rmq_fetch into a host array (sized by a first call when out_cap is None, or the caller's
         uint8 `out`, e.g. page-locked from host_empty: one call, RMQ_ENOSPC if it is too small);
         commit: RMQ_FETCH_COMMIT on every request (the size query commits nothing); replica:
@@ -433,8 +444,13 @@ class Engine:
         request (an array, or one value for all; None or RMQ_OFFSET_NONE entries: the committed
         offset): rmq_fetch_at, FORMAT.md §7; the size query reads at the same offsets. fill:
         RMQ_FETCH_FILL (FORMAT.md §7 "Filling a bounded output": requests are served in order until
-        the output is full, the rest come back RMQ_PENDING); needs out_cap or out (no sizing call)."""
+        the output is full, the rest come back RMQ_PENDING); needs out_cap or out (no sizing call).
+        table: a record table with the fetch (rmq_fetch_table, FORMAT.md §7 "Record table"): True,
+        or the caller's (rec_row, rec_pos[, rec_cap]) uint64 arrays (rec_pos None: the size probe);
+        the call then returns (rc, res, out, bytes_used, rec_row, rec_pos), RMQ_ENOSPC also when
+        rec_row[n] > rec_cap; table_records splits the output with it."""
         n = len(pidx)
+        tab = []  # the table's arrays, once the output's size is known (the size query takes none)
         if fill and out is None and out_cap is None:
             raise ValueError("fill needs out_cap or out: a filling fetch has no sizing call")
         bud = _budgets(max_bytes, n)
@@ -442,6 +458,9 @@ class Engine:
         host = A.RMQ_MEM_HOST | (A.RMQ_FETCH_FILL if fill else 0)
 
         def call(*a):  # rmq_fetch, or rmq_fetch_bytes / rmq_fetch_at with their arrays after the requests
+            if tab:
+                return self.lib.rmq_fetch_table(a[0], a[1], _ptr(at), _ptr(bud), *a[2:7], _ptr(tab[0]), _ptr(tab[1]),
+                                                tab[2], a[7])
             if at is not None:
                 return self.lib.rmq_fetch_at(a[0], a[1], _ptr(at), _ptr(bud), *a[2:])
             if bud is None:
@@ -456,10 +475,12 @@ class Engine:
             if commit:
                 req[:, 3] |= A.RMQ_FETCH_COMMIT
             used = C.c_uint64()
+            if table:
+                tab[:] = _host_table(table, n, out.size)
             rc = call(self.h, _ptr(req), n, host, _ptr(out), out.size, _ptr(res), C.byref(used))
             if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
                 raise EngineError(rc, "rmq_fetch")
-            return rc, res, out, int(used.value)
+            return (rc, res, out, int(used.value)) + (tuple(tab[:2]) if table else ())
         if out_cap is None:
             used = C.c_uint64()
             rc = call(self.h, _ptr(req), n, A.RMQ_MEM_HOST, None, 0, _ptr(res), C.byref(used))
@@ -470,15 +491,17 @@ class Engine:
             req[:, 3] |= A.RMQ_FETCH_COMMIT
         out = np.zeros(max(out_cap, 1), np.uint8)
         used = C.c_uint64()
+        if table:
+            tab[:] = _host_table(table, n, out_cap)
         rc = call(self.h, _ptr(req), n, host, _ptr(out), out_cap, _ptr(res), C.byref(used))
         if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
             raise EngineError(rc, "rmq_fetch")
-        return rc, res, out[:out_cap], int(used.value)
+        return (rc, res, out[:out_cap], int(used.value)) + (tuple(tab[:2]) if table else ())
 
     def fetch_device(self, pidx, consumer, max_records, d_out: int, out_cap: int, commit: bool = False,
                      req: np.ndarray | None = None, res: np.ndarray | None = None, pinned_rows: bool = False,
                      d_rows: tuple | None = None, verify: bool = False, max_bytes=None, offsets=None,
-                     fill: bool = False):
+                     fill: bool = False, table=None):
         """rmq_fetch into a device buffer (16-byte aligned); returns (rc, res, bytes_used). req / res:
         the caller's arrays (pidx / consumer / max_records None leave req's columns as they are);
         pinned_rows: page-locked ones (fetch_rows), read and written by the kernels in place
@@ -488,14 +511,22 @@ class Engine:
         RMQ_FETCH_VERIFY on every request (host rows only). max_bytes: byte budgets of host rows, as
         for fetch. offsets: explicit offsets of host rows, as for fetch (rmq_fetch_at); with d_rows
         the address of a device array (uint64[n], 8-byte aligned). fill: RMQ_FETCH_FILL, as for fetch
-        (every kind of rows)."""
+        (every kind of rows). table = (d_rec_row, d_rec_pos, rec_cap): a record table in device memory
+        (rmq_fetch_table; uint64[n + 1] and uint64[rec_cap], 8-byte aligned; d_rec_pos 0 / None with
+        rec_cap 0: the size probe), with any kind of rows; the two addresses are then returned too."""
+        tb = None if table is None else (C.c_void_p(table[0]), C.c_void_p(table[1] or None), int(table[2]))
+        ret = () if table is None else (table[0], table[1])
         if d_rows is not None:
             n, d_req, d_res = d_rows[:3]
             if max_bytes is not None:
                 raise ValueError("device rows take their budgets as d_rows' fourth element")
             used = C.c_uint64()
             mem = A.RMQ_MEM_DEVICE | A.RMQ_FETCH_DEVICE_ROWS | (A.RMQ_FETCH_FILL if fill else 0)
-            if offsets is not None:
+            if tb is not None:
+                rc = self.lib.rmq_fetch_table(self.h, C.c_void_p(d_req), C.c_void_p(None if offsets is None else int(offsets)),
+                                              C.c_void_p(d_rows[3] if len(d_rows) > 3 and d_rows[3] else None), n, mem,
+                                              d_out, out_cap, C.c_void_p(d_res), *tb, C.byref(used))
+            elif offsets is not None:
                 rc = self.lib.rmq_fetch_at(self.h, C.c_void_p(d_req), C.c_void_p(int(offsets)),
                                            C.c_void_p(d_rows[3] if len(d_rows) > 3 and d_rows[3] else None), n, mem,
                                            d_out, out_cap, C.c_void_p(d_res), C.byref(used))
@@ -507,7 +538,7 @@ class Engine:
                                         C.byref(used))
             if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
                 raise EngineError(rc, "rmq_fetch")
-            return rc, None, int(used.value)
+            return (rc, None, int(used.value)) + ret
         n = len(pidx) if pidx is not None else len(req)
         if req is None:
             req = np.zeros((n, 4), np.uint32)
@@ -523,7 +554,10 @@ class Engine:
         mem = A.RMQ_MEM_DEVICE | (A.RMQ_FETCH_PINNED_ROWS if pinned_rows else 0) | (A.RMQ_FETCH_FILL if fill else 0)
         bud = _budgets(max_bytes, n)
         at = _offsets(offsets, n)
-        if at is not None:
+        if tb is not None:
+            rc = self.lib.rmq_fetch_table(self.h, _ptr_reused(req), _ptr(at), _ptr(bud), n, mem, d_out, out_cap,
+                                          _ptr_reused(res), *tb, C.byref(used))
+        elif at is not None:
             rc = self.lib.rmq_fetch_at(self.h, _ptr_reused(req), _ptr(at), _ptr(bud), n, mem, d_out, out_cap,
                                        _ptr_reused(res), C.byref(used))
         elif bud is None:
@@ -533,12 +567,13 @@ class Engine:
                                           _ptr_reused(res), C.byref(used))
         if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
             raise EngineError(rc, "rmq_fetch")
-        return rc, res, int(used.value)
+        return (rc, res, int(used.value)) + ret
 
     def fetch_async(self, pidx, consumer, max_records, d_out: int | None = None, out_cap: int = 0,
                     out: np.ndarray | None = None, req: np.ndarray | None = None,
                     res: np.ndarray | None = None, pinned_rows: bool = False,
-                    verify: bool = False, max_bytes=None, offsets=None, fill: bool = False) -> "FetchTicket":
+                    verify: bool = False, max_bytes=None, offsets=None, fill: bool = False,
+                    table=None) -> "FetchTicket":
         """rmq_fetch_async into a device buffer (d_out, 16-byte aligned) or a host array (out): the
         call returns at once; fetch_poll(ticket) gives (rc, res, bytes_used) once it completes. The
         handle keeps the request, result and output arrays alive until then. req ([n, 4] uint32)
@@ -549,7 +584,9 @@ class Engine:
         unchanged until the ticket completes. verify: RMQ_FETCH_VERIFY ORed into every request.
         max_bytes: byte budgets, as for fetch (rmq_fetch_bytes_async; read before the call returns).
         offsets: explicit offsets, as for fetch (rmq_fetch_at_async; read before the call returns).
-        fill: RMQ_FETCH_FILL, as for fetch."""
+        fill: RMQ_FETCH_FILL, as for fetch. table: a record table (rmq_fetch_table_async): with a
+        host output as for fetch (True, or the caller's arrays), with d_out as for fetch_device
+        (device addresses); fetch_poll then returns (rc, res, bytes_used, rec_row, rec_pos)."""
         n = len(pidx) if pidx is not None else len(req)
         if pinned_rows and (req is None or res is None):
             raise ValueError("pinned_rows needs the caller's page-locked req and res (fetch_rows)")
@@ -575,7 +612,16 @@ class Engine:
         t = C.c_uint64()
         bud = _budgets(max_bytes, n)
         at = _offsets(offsets, n)
-        if at is not None:
+        if table is not None and table is not False:
+            if d_out is not None:
+                tb = (C.c_void_p(table[0]), C.c_void_p(table[1] or None), int(table[2]))
+                table = (table[0], table[1])
+            else:
+                row, pos, cap = _host_table(table, n, out_cap)
+                tb, table = (_ptr(row), _ptr(pos), cap), (row, pos)
+            _check(self.lib.rmq_fetch_table_async(self.h, _ptr_reused(req), _ptr(at), _ptr(bud), n, mem, ptr, out_cap,
+                                                  _ptr_reused(res), *tb, C.byref(t)), "rmq_fetch_table_async")
+        elif at is not None:
             _check(self.lib.rmq_fetch_at_async(self.h, _ptr_reused(req), _ptr(at), _ptr(bud), n, mem, ptr, out_cap,
                                                _ptr_reused(res), C.byref(t)), "rmq_fetch_at_async")
         elif bud is None:
@@ -584,7 +630,7 @@ class Engine:
         else:
             _check(self.lib.rmq_fetch_bytes_async(self.h, _ptr_reused(req), _ptr(bud), n, mem, ptr, out_cap,
                                                   _ptr_reused(res), C.byref(t)), "rmq_fetch_bytes_async")
-        tk = FetchTicket(t.value, req, res, out)
+        tk = FetchTicket(t.value, req, res, out, table or None)
         self._fetching[t.value] = tk
         return tk
 
@@ -596,7 +642,8 @@ class Engine:
         return req, self.host_empty(n, FETCH_RES_DTYPE)
 
     def fetch_poll(self, tk: "FetchTicket", wait: bool = False):
-        """(rc, res, bytes_used) of an rmq_fetch_async ticket, or None while it runs."""
+        """(rc, res, bytes_used) of an rmq_fetch_async ticket, or None while it runs; a ticket with a
+        record table adds (rec_row, rec_pos)."""
         used = C.c_uint64()
         rc = self.lib.rmq_fetch_poll(self.h, tk.ticket, 1 if wait else 0, C.byref(used))
         if rc == A.RMQ_PENDING:
@@ -604,7 +651,7 @@ class Engine:
         self._fetching.pop(tk.ticket, None)
         if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
             raise EngineError(rc, "rmq_fetch_poll")
-        return rc, tk.res, int(used.value)
+        return (rc, tk.res, int(used.value)) + (tuple(tk.table) if tk.table else ())
 
     def set_segments(self, pidx, segment_bytes) -> None:
         """Ring sizes of partitions pidx[i] (rmq_set_segments: retention at a smaller size first, the
@@ -817,3 +864,28 @@ def parse_records(buf: np.ndarray) -> list[tuple[int, int, bytes]]:
         out.append((off, crc, b[pos + 16:pos + 16 + ln]))
         pos += 16 + ((ln + 15) & ~15)
     return out
+
+
+def table_records(buf: np.ndarray, res: np.ndarray, rec_row: np.ndarray, rec_pos: np.ndarray) -> list:
+    """Split a fetch's output with its record table (rmq_fetch_table, FORMAT.md §7 "Record table"):
+    one list per request, [(offset, crc, payload), ...] as parse_records gives it for that request's
+    run, empty for a request that owns no table words. Every record's position comes from the table
+    by array arithmetic: no length word is chained."""
+    n = len(res)
+    cnt = np.where((res["status"] == A.RMQ_OK) & (res["count"] > 0), res["count"], 0).astype(np.int64)
+    total = int(cnt.sum())
+    if not total:
+        return [[] for _ in range(n)]
+    first = np.concatenate(([0], np.cumsum(cnt)))  # records before each request's
+    req_of = np.repeat(np.arange(n), cnt)
+    k = np.arange(total) - first[req_of]  # ordinal inside the request
+    word = np.asarray(rec_row, np.uint64).astype(np.int64)[req_of] + k
+    start = res["out_pos"].astype(np.int64)[req_of] + np.asarray(rec_pos, np.uint64).astype(np.int64)[word]
+    hdr = np.ascontiguousarray(buf)[start[:, None] + np.arange(16)]  # [total][16] header bytes
+    off = hdr[:, :8].copy().view("<u8").ravel()
+    ln = hdr[:, 8:12].copy().view("<u4").ravel().astype(np.int64)
+    crc = hdr[:, 12:16].copy().view("<u4").ravel()
+    lo = start + 16
+    b = buf.tobytes()
+    recs = [(o, c, b[s:e]) for o, c, s, e in zip(off.tolist(), crc.tolist(), lo.tolist(), (lo + ln).tolist())]
+    return [recs[int(first[r]):int(first[r + 1])] for r in range(n)]

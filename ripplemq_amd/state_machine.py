@@ -34,7 +34,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _abi as A
-from .engine import Engine, EngineConfig, EngineError, parse_records
+from .engine import Engine, EngineConfig, EngineError, parse_records, table_records
 
 NOT_LEADER = "Not leader"
 COMMIT_PENDING = "Commit pending"
@@ -182,7 +182,7 @@ class PartitionBroker:
     def __init__(self, directory: PartitionDirectory, engine=None, *, replication_factor: int = 1,
                  segment_bytes: int = 1 << 22, index_interval: int = 4096, device: int = 0,
                  messages_as_str: bool = True, durable=None, verify: bool = False,
-                 repair: bool = False):
+                 repair: bool = False, record_table: bool = False):
         """verify: reads carry RMQ_FETCH_VERIFY, and a slice with a record that fails its CRC32C or
         framing is answered by a failed MessageBatchReadResponse (no messages, the offset the
         consumer stands at, an error message) instead of being served. Off by default.
@@ -193,7 +193,10 @@ class PartitionBroker:
         rmq_repair is collective, and a read processor cannot make every rank call it. Off by default.
         durable: a ``ripplemq_amd.tier.DurableLog`` over this engine, or None. With it, a read
         below a ring's retained start is served from the segment files (the reference never
-        evicts, PartitionStateMachine.java:26) instead of failing with RMQ_EOFFSET."""
+        evicts, PartitionStateMachine.java:26) instead of failing with RMQ_EOFFSET.
+        record_table: reads fetch with a record table (rmq_fetch_table, FORMAT.md §7 "Record table")
+        and are split into messages with it (table_records) instead of by chaining length words per
+        record (parse_records); the responses are the same. Off by default."""
         self.dir = directory
         self.durable = durable
         if engine is None:
@@ -205,6 +208,7 @@ class PartitionBroker:
         self.as_str = messages_as_str
         self.verify = bool(verify)
         self.repair = bool(repair)
+        self.record_table = bool(record_table)
         self._sms: dict[str, PartitionStateMachine] = {}
 
     def close(self) -> None:
@@ -321,22 +325,26 @@ class PartitionBroker:
             c.append(self.dir.consumer(req.getConsumerId()))
             mx.append(max(int(req.getMaxMessages()), 0))
         if idx:
-            _, res, buf, _ = self.engine.fetch(np.asarray(p, np.uint32), np.asarray(c, np.uint32),
-                                               np.asarray(mx, np.uint32), **({"verify": True} if self.verify else {}))
-            rows = [(res, buf, k) for k in range(len(idx))]
+            kw = {"table": True} if self.record_table else {}
+            _, res, buf, _, *tab = self.engine.fetch(np.asarray(p, np.uint32), np.asarray(c, np.uint32),
+                                                     np.asarray(mx, np.uint32), **kw,
+                                                     **({"verify": True} if self.verify else {}))
+            split = table_records(buf, res, *tab) if tab else None  # every request's records, by the table
+            rows = [(res, buf, k, split) for k in range(len(idx))]
             bad = [k for k in range(len(idx)) if int(res["status"][k]) == A.RMQ_ECORRUPT]
             if bad and self.verify and self.repair:
                 # heal the refused partitions from their clean local replicas, then read those again
                 for pi in sorted({p[k] for k in bad}):
                     self.engine.repair(pi, 1)
-                _, res2, buf2, _ = self.engine.fetch(np.asarray([p[k] for k in bad], np.uint32),
-                                                     np.asarray([c[k] for k in bad], np.uint32),
-                                                     np.asarray([mx[k] for k in bad], np.uint32), verify=True)
+                _, res2, buf2, _, *tab2 = self.engine.fetch(np.asarray([p[k] for k in bad], np.uint32),
+                                                            np.asarray([c[k] for k in bad], np.uint32),
+                                                            np.asarray([mx[k] for k in bad], np.uint32), verify=True, **kw)
+                split2 = table_records(buf2, res2, *tab2) if tab2 else None
                 for j, k in enumerate(bad):
-                    rows[k] = (res2, buf2, j)
+                    rows[k] = (res2, buf2, j, split2)
             spilled = False
             for kk, r in enumerate(idx):
-                res, buf, k = rows[kk]
+                res, buf, k, split = rows[kk]
                 st = int(res["status"][k])
                 if st == A.RMQ_ENOTLEADER:
                     out[r] = NOT_LEADER
@@ -361,7 +369,7 @@ class PartitionBroker:
                 if st != A.RMQ_OK:
                     raise EngineError(st, f"fetch {requests[r].getGroupId()}")
                 pos, nb = int(res["out_pos"][k]), int(res["bytes"][k])
-                recs = parse_records(buf[pos:pos + nb])
+                recs = split[k] if split is not None else parse_records(buf[pos:pos + nb])
                 out[r] = MessageBatchReadResponse([_decode(b, self.as_str) for _, _, b in recs],
                                                   int(res["start_offset"][k]))
         return out
