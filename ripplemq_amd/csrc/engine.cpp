@@ -11,7 +11,8 @@
 // append path: launch k reports launch k-1 complete through a host-visible word, and the tail is
 // read with hipStreamQuery. Control-plane calls (leadership, replicas, acks, consumer offsets,
 // fetch) flush and drain first and run synchronously: they are rare next to the append stream.
-// The audit calls (scrub, repair, reindex, remote repair, restore) are in audit.cpp.
+// The fetch calls (their slots, staging and launches) are in fetch.cpp; the audit calls (scrub,
+// repair, reindex, remote repair, restore) are in audit.cpp.
 #include <chrono>
 
 #include "engine_internal.hpp"
@@ -428,27 +429,6 @@ int late_retention(rmq_engine* e) {
   return RMQ_OK;
 }
 
-// The asynchronous fetches held back (fetch_issue) as ONE resolve + gather pair (kFetchBatch tickets
-// at most), each ticket's completion event after it. Called (under mu) by the next fetch that cannot
-// join them, by every other call that takes the engine lock (EngineLock: whatever it issues on the
-// pipeline stream stays ordered after the fetches issued before it), and by a poll of a held ticket.
-int fetch_flush(rmq_engine* e) {
-  if (e->fpend.empty()) return RMQ_OK;
-  int rc = late_retention(e);
-  if (rc) return rc;
-  FetchArgs t[kFetchBatch];
-  uint32_t nt = 0;
-  for (uint32_t i : e->fpend) t[nt++] = e->fslot[i].args;
-  launch_fetch_batch(t, nt, e->main_s);
-  HIP_TRY(hipGetLastError());
-  for (uint32_t i : e->fpend) {
-    HIP_TRY(hipEventRecord(e->fslot[i].ev, e->main_s));
-    e->fslot[i].pending = false;
-  }
-  e->fpend.clear();
-  return RMQ_OK;
-}
-
 // Wait for everything issued on the pipeline stream, without flushing batches that are still
 // forming or in the pipeline's earlier stages (reads of committed state, consumer commits).
 int quiesce(rmq_engine* e) {
@@ -589,19 +569,7 @@ void free_engine(rmq_engine* e) {
   audit_free(e);
   repair_remote_free(e);
   if (e->state_stage) hipHostFree(e->state_stage);
-  for (rmq_engine::FetchSlot& f : e->fslot) {
-    void* fs[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_out, f.d_bud, f.d_at, f.d_csum_fill,
-                  f.d_tsum, f.d_trow, f.d_tpos};
-    for (void* p : fs) bufs.push_back(p);
-    if (f.h_bud) hipHostFree(f.h_bud);
-    if (f.h_at) hipHostFree(f.h_at);
-    if (f.h_req) hipHostFree(f.h_req);
-    if (f.h_res) hipHostFree(f.h_res);
-    if (f.ev) hipEventDestroy(f.ev);
-    if (f.ev_copy) hipEventDestroy(f.ev_copy);
-    if (f.ev_in) hipEventDestroy(f.ev_in);
-    if (f.ev_k) hipEventDestroy(f.ev_k);
-  }
+  fetch_free(e);
   for (const StateSet& z : e->sets) {
     bufs.push_back(z.leo);
     bufs.push_back(z.used);
@@ -1610,589 +1578,6 @@ int rmq_commit_consumer_offset(rmq_engine* e, const uint32_t* pidx, const uint32
   }
   const int rc = check_err(e);
   return rc ? rc : rc_all;
-}
-
-namespace {
-
-// Scratch of a fetch slot for n requests and, for a host output, out_cap bytes of device staging.
-// Plain hipMalloc (no zeroing, no device synchronisation: a slot first used while the pipeline
-// runs must not wait for it; every word a fetch reads is written by it first).
-int fetch_alloc(void** p, size_t bytes) {
-  *p = nullptr;
-  HIP_TRY(hipMalloc(p, std::max<size_t>(bytes, 16)));
-  return RMQ_OK;
-}
-
-int fetch_slot_reserve(rmq_engine::FetchSlot& f, uint32_t n, uint64_t stage, hipStream_t s) {
-  if (n > f.cap) {
-    void* ds[] = {f.d_req, f.d_res, f.d_aux, f.d_cpre, f.d_csum, f.d_bud, f.d_at, f.d_csum_fill, f.d_tsum, f.d_trow};
-    for (void* p : ds)
-      if (p) hipFree(p);
-    if (f.h_req) hipHostFree(f.h_req);
-    if (f.h_res) hipHostFree(f.h_res);
-    if (f.h_bud) hipHostFree(f.h_bud);
-    if (f.h_at) hipHostFree(f.h_at);
-    f.d_req = f.d_cpre = f.h_req = f.h_bud = f.d_bud = nullptr;
-    f.d_res = f.d_aux = f.d_csum = f.h_res = f.h_at = f.d_at = f.d_csum_fill = f.d_tsum = f.d_trow = nullptr;
-    f.cap = 0;
-    const uint32_t cap = std::max<uint32_t>(n, 1024);
-    int rc = fetch_alloc((void**)&f.d_req, (size_t)cap * 16);
-    if (!rc) rc = fetch_alloc((void**)&f.d_res, ((size_t)cap * 4 + 2) * 8);
-    if (!rc) rc = fetch_alloc((void**)&f.d_aux, (size_t)cap * 16);
-    if (!rc) rc = fetch_alloc((void**)&f.d_cpre, ((size_t)cap + 4) * 4);
-    const uint32_t lines = cap / kFetchChunk + 2;
-    if (!rc) rc = fetch_alloc((void**)&f.d_csum, 2ull * lines * kCsumStride * 8);
-    if (!rc) rc = fetch_alloc((void**)&f.d_bud, (size_t)cap * 4);
-    if (rc) return rc;
-    // both halves start zeroed (stream-ordered before the slot's first fetch)
-    HIP_TRY(hipMemsetAsync(f.d_csum, 0, 2ull * lines * kCsumStride * 8, s));
-    f.csum_lines = lines;
-    f.csum_par = 0;
-    HIP_TRY(hipHostMalloc((void**)&f.h_req, (size_t)cap * 16, 0));
-    HIP_TRY(hipHostMalloc((void**)&f.h_res, ((size_t)cap * 4 + 2) * 8, 0));  // res, bytes needed
-    HIP_TRY(hipHostMalloc((void**)&f.h_bud, (size_t)cap * 4, 0));
-    f.cap = cap;
-  }
-  if (stage > f.out_alloc) {
-    if (f.d_out) hipFree(f.d_out);
-    f.d_out = nullptr;
-    f.out_alloc = 0;
-    const int rc = fetch_alloc((void**)&f.d_out, stage);
-    if (rc) return rc;
-    f.out_alloc = stage;
-  }
-  return RMQ_OK;
-}
-
-// Advance the fetch in slot f (fetch_mu held): RMQ_PENDING while its kernels or host copies run
-// (wait: block instead); else its result, with the caller's res (and host output) filled and the
-// slot idle again.
-int fetch_slot_step(rmq_engine* e, rmq_engine::FetchSlot& f, bool wait, uint64_t* bytes_used) {
-  if (f.phase == 1) {
-    std::lock_guard<std::mutex> g(e->mu);  // a held-back ticket is launched (with the others held) when polled
-    if (f.pending) {
-      const int rc = fetch_flush(e);
-      if (rc) return rc;
-    }
-  }
-  if (f.phase == 1) {
-    if (wait) {
-      const int rc = event_wait(f.ev);
-      if (rc) return rc;
-    } else {
-      const hipError_t q = hipEventQuery(f.ev);
-      if (q == hipErrorNotReady) return RMQ_PENDING;
-      HIP_TRY(q);
-    }
-    // the device writes rmq_fetch_res rows (status zero-extended into its reserved word)
-    static_assert(sizeof(rmq_fetch_res) == 32, "result rows are four words");
-    if (!f.rows_pinned) std::memcpy(f.res, f.h_res, (size_t)f.n * 32);  // (pinned: written in place)
-    // some request did not fit iff the bytes needed exceed the output (requests are placed in
-    // order: the one holding byte out_cap is cut), so no pass over the rows
-    f.rc = __atomic_load_n(f.need, __ATOMIC_ACQUIRE) > f.out_cap ? RMQ_ENOSPC : RMQ_OK;
-    // (a table that needs more words than rec_cap: the same code, told apart by rec_row[n] > rec_cap)
-    if (f.table && __atomic_load_n(f.tneed, __ATOMIC_ACQUIRE) > f.t_cap) f.rc = RMQ_ENOSPC;
-    f.phase = 2;
-    if (f.mem == RMQ_MEM_HOST && (f.out_cap || f.t_row)) {
-      if (f.t_row) {
-        // a host table: rec_row whole, and of rec_pos the words the walk wrote: rows fit while
-        // their prefix does (the prefix rises with r), so those are the words before the first row
-        // that does not; the others stay untouched in the caller's array, as on the device
-        uint64_t words = 0;
-        for (uint32_t r = 0; r < f.n; ++r) {
-          const uint64_t w = f.res[r].status == RMQ_OK && f.res[r].count ? (uint64_t)f.res[r].count + 1 : 0;
-          if (w > f.t_cap - words) break;
-          words += w;
-        }
-        HIP_TRY(hipMemcpyAsync(f.t_row, f.d_trow, ((size_t)f.n + 1) * 8, hipMemcpyDeviceToHost, e->fetch_out_s));
-        if (words) HIP_TRY(hipMemcpyAsync(f.t_pos, f.d_tpos, (size_t)words * 8, hipMemcpyDeviceToHost, e->fetch_out_s));
-      }
-      // copy back the byte runs of the served requests only: the regions of requests that did not
-      // fit stay untouched in the caller's buffer, as with a device buffer the gather writes itself
-      uint64_t lo = 0, hi = 0;
-      for (uint32_t r = 0; f.out_cap && r <= f.n; ++r) {
-        const bool served = r < f.n && f.res[r].status == RMQ_OK && f.res[r].bytes;
-        if (served && f.res[r].out_pos == hi && hi > lo) {
-          hi += f.res[r].bytes;
-          continue;
-        }
-        if (hi > lo) HIP_TRY(hipMemcpyAsync(f.out + lo, f.d_out + lo, hi - lo, hipMemcpyDeviceToHost, e->fetch_out_s));
-        lo = hi = served ? f.res[r].out_pos : 0;
-        if (served) hi += f.res[r].bytes;
-      }
-      HIP_TRY(hipEventRecord(f.ev_copy, e->fetch_out_s));
-    } else {
-      f.phase = 3;  // nothing to copy
-    }
-  }
-  if (f.phase == 2) {
-    if (wait) {
-      const int rc = event_wait(f.ev_copy);
-      if (rc) return rc;
-    } else {
-      const hipError_t q = hipEventQuery(f.ev_copy);
-      if (q == hipErrorNotReady) return RMQ_PENDING;
-      HIP_TRY(q);
-    }
-  }
-  if (bytes_used) *bytes_used = __atomic_load_n(f.need, __ATOMIC_ACQUIRE);
-  f.phase = 0;
-  f.ticket = 0;
-  return f.rc;
-}
-
-}  // namespace
-
-namespace {
-// Issue a fetch into the next slot: its kernels on the pipeline stream, an event after them.
-// max_bytes: the requests' byte budgets (rmq_fetch_bytes, FORMAT.md §7), or null: none.
-// offsets: the requests' explicit offsets (rmq_fetch_at, FORMAT.md §7), or null: none.
-// rec_row, rec_pos, rec_cap: the record table (rmq_fetch_table, FORMAT.md §7), or null, null, 0: none.
-int fetch_issue(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
-                uint32_t n, uint32_t mem,
-                uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket, bool sync,
-                uint64_t* rec_row = nullptr, uint64_t* rec_pos = nullptr, uint64_t rec_cap = 0) {
-  if (!e || !ticket) return RMQ_EINVAL;
-  const bool table = rec_row != nullptr;
-  if (!rec_row && (rec_pos || rec_cap)) return RMQ_EINVAL;
-  if (!rec_pos && rec_cap) return RMQ_EINVAL;  // (rec_pos null with rec_cap 0: a size probe)
-  if ((mem & 3u) == RMQ_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(rec_row) | reinterpret_cast<uintptr_t>(rec_pos)) & 7u))
-    return RMQ_EINVAL;
-  bool rows_pinned = (mem & RMQ_FETCH_PINNED_ROWS) != 0;
-  const bool rows_dev = (mem & RMQ_FETCH_DEVICE_ROWS) != 0;
-  const bool fill = (mem & RMQ_FETCH_FILL) != 0;  // (FORMAT.md §7 "Filling a bounded output")
-  mem &= ~(RMQ_FETCH_PINNED_ROWS | RMQ_FETCH_DEVICE_ROWS | RMQ_FETCH_FILL);
-  if (rows_dev && (rows_pinned || mem != RMQ_MEM_DEVICE)) return RMQ_EINVAL;  // (output on the device too)
-  if (rows_dev && (reinterpret_cast<uintptr_t>(max_bytes) & 3u)) return RMQ_EINVAL;
-  if (rows_dev && (reinterpret_cast<uintptr_t>(offsets) & 7u)) return RMQ_EINVAL;
-  if ((n && (!reqs || !res)) || (mem != RMQ_MEM_HOST && mem != RMQ_MEM_DEVICE)) return RMQ_EINVAL;
-  if (out_cap && !out) return RMQ_EINVAL;
-  if (mem == RMQ_MEM_DEVICE && (reinterpret_cast<uintptr_t>(out) & 15u)) return RMQ_EINVAL;
-  std::lock_guard<std::mutex> fg(e->fetch_mu);
-  HIP_TRY(hipSetDevice(e->device));
-  rmq_engine::FetchSlot& f = e->fslot[e->fslot_next];
-  if (f.ticket) {  // every slot taken: complete the oldest into its caller's arrays, keep its result
-    uint64_t used = 0;
-    const uint64_t old = f.ticket;
-    const int rc = fetch_slot_step(e, f, true, &used);
-    if (rc < 0 && rc != RMQ_ENOSPC) return rc;
-    e->fetch_done.push_back({old, (uint64_t)(int64_t)rc, used});
-  }
-  // RMQ_FETCH_COMMIT: known flags only, one committing request per (partition, consumer)
-  bool any = false, replica = false, verify = false;
-  if (!rows_dev) {  // (device rows: never read here; their flags are ignored)
-    // the OR of every row's flags word (the high half of its second 8-byte word), four rows per
-    // step with no early exit: 16,384 rows in a few us instead of a branch per row
-    static_assert(sizeof(rmq_fetch_req) == 16 && offsetof(rmq_fetch_req, flags) == 12, "request rows are four words");
-    typedef uint64_t __attribute__((__may_alias__)) u64a;
-    const u64a* w = reinterpret_cast<const u64a*>(reqs);
-    uint64_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
-    uint32_t r = 0;
-    for (; r + 4 <= n; r += 4) {
-      a0 |= w[2 * r + 1];
-      a1 |= w[2 * r + 3];
-      a2 |= w[2 * r + 5];
-      a3 |= w[2 * r + 7];
-    }
-    for (; r < n; ++r) a0 |= w[2 * r + 1];
-    const uint32_t fl = (uint32_t)((a0 | a1 | a2 | a3) >> 32);
-    if (fl & ~(RMQ_FETCH_COMMIT | RMQ_FETCH_REPLICA | RMQ_FETCH_VERIFY)) return RMQ_EINVAL;
-    any = (fl & RMQ_FETCH_COMMIT) != 0;
-    replica = (fl & RMQ_FETCH_REPLICA) != 0;
-    verify = (fl & RMQ_FETCH_VERIFY) != 0;
-    if (any) {
-      const size_t slots = (size_t)e->cfg.num_partitions * e->cfg.max_consumers;
-      if (e->fetch_stamp.size() != slots) {
-        e->fetch_stamp.assign(slots, 0u);
-        e->fetch_stamp_rep.assign(e->cfg.num_partitions, 0u);
-        e->fetch_gen = 0;
-      }
-      if (++e->fetch_gen == 0) {
-        std::fill(e->fetch_stamp.begin(), e->fetch_stamp.end(), 0u);
-        std::fill(e->fetch_stamp_rep.begin(), e->fetch_stamp_rep.end(), 0u);
-        e->fetch_gen = 1;
-      }
-      for (uint32_t r = 0; r < n; ++r) {
-        const rmq_fetch_req& q = reqs[r];
-        if (!(q.flags & RMQ_FETCH_COMMIT) || q.pidx >= e->cfg.num_partitions || q.consumer >= e->cfg.max_consumers)
-          continue;
-        // a replica read commits the partition's replica cursor: one per partition (any consumer key)
-        uint32_t& sl = (q.flags & RMQ_FETCH_REPLICA) ? e->fetch_stamp_rep[q.pidx]
-                                                     : e->fetch_stamp[(size_t)q.pidx * e->cfg.max_consumers + q.consumer];
-        if (sl == e->fetch_gen) return RMQ_EINVAL;
-        sl = e->fetch_gen;
-      }
-    }
-  }
-  const uint64_t tk = ++e->fetch_seq;
-  if (!n) {  // nothing to fetch: complete at once
-    if (table && mem == RMQ_MEM_HOST) rec_row[0] = 0;  // (rec_row has n + 1 words)
-    if (table && mem == RMQ_MEM_DEVICE) HIP_TRY(hipMemset(rec_row, 0, 8));
-    e->fetch_done.push_back({tk, (uint64_t)(int64_t)RMQ_OK, 0});
-    while (e->fetch_done.size() > 256) e->fetch_done.pop_front();
-    *ticket = tk;
-    return RMQ_OK;
-  }
-  int rc = fetch_slot_reserve(f, n, mem == RMQ_MEM_HOST ? out_cap : 0, e->main_s);
-  if (rc) return rc;
-  uint8_t* d_out = mem == RMQ_MEM_HOST ? (out_cap ? f.d_out : nullptr) : out;
-  // Host rows are page-locked: the caller's own (RMQ_FETCH_PINNED_ROWS, if the runtime maps them),
-  // else the slot's staging rows. The kernels read and write them in place across PCIe (no copy
-  // either way: the lowest latency for one call), or (RMQ_FETCH_DMA, asynchronous calls by
-  // default) the request rows go to the slot's device rows by DMA on the copy stream and the
-  // result rows come back by DMA on the result stream, so the kernels touch device memory only
-  // and a burst's copies overlap the other fetches' kernels.
-  void* d_rq = nullptr;
-  void* d_rs = nullptr;
-  if (rows_dev) {
-    d_rq = const_cast<rmq_fetch_req*>(reqs);
-    d_rs = res;
-  } else if (rows_pinned && (hipHostGetDevicePointer(&d_rq, const_cast<rmq_fetch_req*>(reqs), 0) != hipSuccess ||
-                      hipHostGetDevicePointer(&d_rs, res, 0) != hipSuccess)) {
-    (void)hipGetLastError();
-    rows_pinned = false;  // not mapped: staged like ordinary rows
-  }
-  if (!rows_pinned && !rows_dev) {
-    std::memcpy(f.h_req, reqs, (size_t)n * sizeof(rmq_fetch_req));
-    d_rq = f.h_req;
-    d_rs = f.h_res;
-  }
-  const bool dma = !rows_dev && (e->fetch_dma >= 2 || (e->fetch_dma == 1 && !sync));
-  void* h_rs = rows_pinned ? static_cast<void*>(res) : static_cast<void*>(f.h_res);  // (DMA) result rows' host copy
-  const bool dma_in = dma && e->fetch_dma_in;
-  // Byte budgets. Host rows: copied now into the slot's page-locked words (the caller's array is
-  // its own again when the call returns), which the trim kernel reads in place, or which go to the
-  // device with the request rows (RMQ_FETCH_DMA); budgets that are all zero are no budgets.
-  // Device rows: read where they are.
-  const uint32_t* d_bud = nullptr;
-  if (max_bytes && rows_dev) {
-    d_bud = max_bytes;
-  } else if (max_bytes) {
-    uint32_t some = 0;
-    for (uint32_t r = 0; r < n; ++r) some |= (f.h_bud[r] = max_bytes[r]);
-    if (some) d_bud = f.h_bud;
-    if (some && dma_in) {
-      HIP_TRY(hipMemcpyAsync(f.d_bud, f.h_bud, (size_t)n * 4, hipMemcpyHostToDevice, e->copy_s));
-      d_bud = f.d_bud;
-    }
-  }
-  // Explicit offsets, as the budgets. Host rows: copied now into the slot's page-locked words, which
-  // the resolve reads in place (or which go to the device with the request rows); offsets that are
-  // all RMQ_OFFSET_NONE are no offsets. Device rows: read where they are.
-  const uint64_t* d_at = nullptr;
-  if (offsets && rows_dev) {
-    d_at = offsets;
-  } else if (offsets) {
-    // (the slot's offset words are made by its first call that passes offsets: a slot that never
-    // sees one holds the scratch it always held; fetch_slot_reserve frees them when the slot grows)
-    if (!f.h_at) HIP_TRY(hipHostMalloc((void**)&f.h_at, (size_t)f.cap * 8, 0));
-    if (!f.d_at && dma_in) {
-      rc = fetch_alloc((void**)&f.d_at, (size_t)f.cap * 8);
-      if (rc) return rc;
-    }
-    uint64_t all = ~0ull;
-    for (uint32_t r = 0; r < n; ++r) all &= (f.h_at[r] = offsets[r]);
-    if (all != RMQ_OFFSET_NONE) d_at = f.h_at;
-    if (d_at && dma_in) {
-      HIP_TRY(hipMemcpyAsync(f.d_at, f.h_at, (size_t)n * 8, hipMemcpyHostToDevice, e->copy_s));
-      d_at = f.d_at;
-    }
-  }
-  // (the chunk sums a filling call's gather reads: made by the slot's first filling call, as the
-  // offset words; fetch_slot_reserve frees them when the slot grows)
-  if (fill && !f.d_csum_fill) {
-    rc = fetch_alloc((void**)&f.d_csum_fill, (size_t)f.csum_lines * kCsumStride * 8);
-    if (rc) return rc;
-  }
-  // (the record table's chunk words, and the device staging of a host table: made by the slot's
-  // first table call, or its first with host arrays; the staged rec_pos grows as the staged output)
-  uint64_t* d_trow = rec_row;
-  uint64_t* d_tpos = rec_pos;
-  if (table && !f.d_tsum) {
-    rc = fetch_alloc((void**)&f.d_tsum, (size_t)f.csum_lines * 8);
-    if (rc) return rc;
-  }
-  if (table && mem == RMQ_MEM_HOST) {
-    if (!f.d_trow) {
-      rc = fetch_alloc((void**)&f.d_trow, ((size_t)f.cap + 1) * 8);
-      if (rc) return rc;
-    }
-    if (rec_cap > f.tpos_alloc) {
-      if (f.d_tpos) hipFree(f.d_tpos);
-      f.d_tpos = nullptr;
-      f.tpos_alloc = 0;
-      if (rec_cap > (1ull << 60)) return RMQ_ENOMEM;
-      rc = fetch_alloc((void**)&f.d_tpos, (size_t)rec_cap * 8);
-      if (rc) return rc;
-      f.tpos_alloc = rec_cap;
-    }
-    d_trow = f.d_trow;
-    d_tpos = rec_pos ? f.d_tpos : nullptr;
-  }
-  if (dma_in) {
-    HIP_TRY(hipMemcpyAsync(f.d_req, rows_pinned ? static_cast<const void*>(reqs) : static_cast<const void*>(f.h_req),
-                           (size_t)n * sizeof(rmq_fetch_req), hipMemcpyHostToDevice, e->copy_s));
-    HIP_TRY(hipEventRecord(f.ev_in, e->copy_s));
-    d_rq = f.d_req;
-  }
-  if (dma) d_rs = f.d_res;  // (the gather reads a request's resolve words, then writes its final row there)
-  {
-    // Order against the append pipeline without flushing it: on the pipeline's stream, after the
-    // last launch issued so far and before the next, so no ring bytes or log starts it reads change
-    // under it.
-    std::lock_guard<std::mutex> g(e->mu);  // (not EngineLock: this decides about the held-back fetches)
-    // an asynchronous fetch that commits nothing waits to go with the next ones (up to kFetchBatch
-    // tickets in one resolve + gather pair: the requests of different tickets never depend on one
-    // another); anything else launches the held ones first, then itself
-    // (nor does one with an RMQ_FETCH_VERIFY request: its third kernel follows its own gather)
-    // (nor one with byte budgets: its trim kernel runs between its own resolve and gather)
-    // (nor one that passes an offsets array: only the single-ticket resolve reads them; an array
-    // whose entries are all RMQ_OFFSET_NONE is read by nothing and launches the plain resolve, but
-    // the call is still not held: FORMAT.md §7 says so of every call with offsets != NULL)
-    // (nor one that fills its output: its fill kernel runs before its own gather)
-    // (nor one with a record table: its table kernels follow its own gather and verify)
-    const bool hold =
-        !sync && !any && !verify && !d_bud && !offsets && !fill && !table && !dma && !e->profile && e->fetch_coalesce > 1;
-    if (!hold) {
-      rc = fetch_flush(e);
-      if (rc) return rc;
-    }
-    if (dma_in) HIP_TRY(hipStreamWaitEvent(e->main_s, f.ev_in, 0));
-    if (!hold) {
-      rc = late_retention(e);  // (the log starts the fetch reads: every batch applied so far retained)
-      if (rc) return rc;
-    }
-    FetchArgs a{};
-    a.st = e->st;
-    a.req = static_cast<const uint32_t*>(d_rq);
-    a.req_dev = f.d_req;
-    a.res = f.d_res;
-    a.res_host = static_cast<uint64_t*>(d_rs);
-    a.aux = f.d_aux;
-    a.cpre = f.d_cpre;
-    a.csum_lines = f.csum_lines;
-    a.out = d_out;
-    a.out_cap = out_cap;
-    a.need_host = f.need_dev;
-    a.n = n;
-    // (a ticket with an RMQ_FETCH_VERIFY request: the verify kernel commits, after its verdicts)
-    a.commits = any && !verify ? 1u : 0u;
-    a.replica = replica ? 1u : 0u;
-    a.at = d_at;
-    if (hold) {
-      const size_t half = (size_t)f.csum_lines * kCsumStride;
-      a.csum = f.d_csum + half * f.csum_par;
-      a.csum_next = f.d_csum + half * (f.csum_par ^ 1u);
-      f.csum_par ^= 1u;
-      f.args = a;
-      f.pending = true;
-      e->fpend.push_back(e->fslot_next);
-      if (e->fpend.size() >= std::min<uint32_t>(kFetchBatch, e->fetch_coalesce)) {
-        rc = fetch_flush(e);
-        if (rc) return rc;
-      }
-    }
-    hipEvent_t ev[4] = {}, r0 = nullptr, r1 = nullptr;
-    // (profiling replays a fetch's kernels back to back; a committing fetch runs once: each run
-    // would commit again and the next would read from the committed offset)
-    // (nor is a verifying one replayed: its third kernel rewrites the rows the gather wrote)
-    // (nor a budgeted one: its three kernels are launched without dispatch spans; nor a filling one;
-    // nor one with a record table: its rows feed the table kernels once)
-    const uint32_t runs = hold ? 0u : e->profile && !any && !verify && !d_bud && !fill && !table ? e->fetch_replay : 1u;
-    // (a committing fetch records no dispatch spans: the events the kernels' own dispatches record
-    // were measured to hold the second kernel ~10 us behind the first, which its one run would carry)
-    const bool spans = e->profile && !any && !verify && !d_bud && !fill && !table;
-    if (e->profile) {  // kernel 3: the first run's dispatch spans; 4: every run
-      if (spans) {
-        for (hipEvent_t& x : ev) x = pool_event(e);
-        for (int k = 0; k < 2; ++k) e->prof[3].push_back({ev[2 * k], ev[2 * k + 1]});
-      }
-      r0 = pool_event(e);
-      r1 = pool_event(e);
-      e->prof[4].push_back({r0, r1});
-      e->prof_fetch_runs += runs;
-      HIP_TRY(hipEventRecord(r0, e->main_s));
-    }
-    for (uint32_t k = 0; k < runs; ++k) {
-      const size_t half = (size_t)f.csum_lines * kCsumStride;
-      a.csum = f.d_csum + half * f.csum_par;
-      a.csum_next = f.d_csum + half * (f.csum_par ^ 1u);
-      f.csum_par ^= 1u;
-      if (d_bud || fill) {  // resolve, trim (budgets), fill (a filling call), gather
-        FetchTrimArgs t{};
-        t.st = e->st;
-        t.budget = d_bud;
-        t.req_dev = f.d_req;
-        t.res = f.d_res;
-        t.aux = f.d_aux;
-        t.cpre = f.d_cpre;
-        t.csum = a.csum;
-        t.n = n;
-        if (fill) {
-          FetchFillArgs ff{};
-          ff.t = t;
-          ff.csum_out = f.d_csum_fill;
-          ff.out_cap = out_cap;
-          ff.verify = verify ? 1u : 0u;
-          launch_fetch_fill(a, ff, e->main_s);
-        } else {
-          launch_fetch_budget(a, t, e->main_s);
-        }
-      } else {
-        launch_fetch(a, e->main_s, spans && k == 0 ? ev : nullptr);
-      }
-      HIP_TRY(hipGetLastError());
-    }
-    if (verify) {  // the flagged slices checked in the output, then the ticket's commits
-      FetchVerifyArgs v{};
-      v.st = e->st;
-      v.req_dev = f.d_req;
-      v.rows = a.res_host;
-      v.out = d_out;
-      v.crc = e->d_crc;
-      v.n = n;
-      v.commits = any ? 1u : 0u;
-      v.replica = a.replica;
-      launch_fetch_verify(v, audit_wgs(e), e->main_s);
-      HIP_TRY(hipGetLastError());
-    }
-    if (table) {  // the record table from the final rows (kernel 9: the span of its kernels)
-      FetchTableArgs t{};
-      t.rows = a.res_host;
-      t.out = d_out;
-      t.rec_row = d_trow;
-      t.rec_pos = d_tpos;
-      t.rec_cap = rec_cap;
-      t.tsum = f.d_tsum;
-      t.need_host = f.tneed_dev;
-      t.n = n;
-      hipEvent_t t0 = nullptr, t1 = nullptr;
-      if (e->profile) {
-        t0 = pool_event(e);
-        t1 = pool_event(e);
-        e->prof[9].push_back({t0, t1});
-        HIP_TRY(hipEventRecord(t0, e->main_s));
-      }
-      launch_fetch_table(t, audit_wgs(e), e->main_s);
-      HIP_TRY(hipGetLastError());
-      if (e->profile) HIP_TRY(hipEventRecord(t1, e->main_s));
-    }
-    if (e->profile) HIP_TRY(hipEventRecord(r1, e->main_s));
-    if (hold) {
-      // (the completion event: recorded when fetch_flush launches the kernels)
-    } else if (dma) {  // the result rows to the host behind the kernels, off the pipeline stream
-      HIP_TRY(hipEventRecord(f.ev_k, e->main_s));
-      HIP_TRY(hipStreamWaitEvent(e->fetch_out_s, f.ev_k, 0));
-      HIP_TRY(hipMemcpyAsync(h_rs, f.d_res, (size_t)n * sizeof(rmq_fetch_res), hipMemcpyDeviceToHost, e->fetch_out_s));
-      HIP_TRY(hipEventRecord(f.ev, e->fetch_out_s));
-    } else {
-      HIP_TRY(hipEventRecord(f.ev, e->main_s));  // kernels done: result rows and bytes needed in place
-    }
-  }
-  f.rows_pinned = rows_pinned || rows_dev;  // (no copy of the rows at completion)
-  f.ticket = tk;
-  f.phase = 1;
-  f.rc = RMQ_OK;
-  f.n = n;
-  f.mem = mem;
-  f.out = out;
-  f.out_cap = out_cap;
-  f.res = res;
-  f.table = table;
-  f.t_row = table && mem == RMQ_MEM_HOST ? rec_row : nullptr;
-  f.t_pos = rec_pos;
-  f.t_cap = rec_cap;
-  e->fslot_next = (e->fslot_next + 1) % rmq_engine::kFetchSlots;
-  while (e->fetch_done.size() > 256) e->fetch_done.pop_front();
-  *ticket = tk;
-  return RMQ_OK;
-}
-
-}  // namespace
-
-int rmq_fetch_async(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t mem, uint8_t* out,
-                    uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket) {
-  return fetch_issue(e, reqs, nullptr, nullptr, n, mem, out, out_cap, res, ticket, false);
-}
-
-int rmq_fetch_bytes_async(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* max_bytes, uint32_t n,
-                          uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket) {
-  return fetch_issue(e, reqs, nullptr, max_bytes, n, mem, out, out_cap, res, ticket, false);
-}
-
-int rmq_fetch_at_async(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
-                       uint32_t n, uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* ticket) {
-  return fetch_issue(e, reqs, offsets, max_bytes, n, mem, out, out_cap, res, ticket, false);
-}
-
-int rmq_fetch_poll(rmq_engine* e, uint64_t ticket, uint32_t wait, uint64_t* bytes_used) {
-  if (!e || !ticket) return RMQ_EINVAL;
-  std::lock_guard<std::mutex> fg(e->fetch_mu);
-  if (bytes_used) *bytes_used = 0;
-  for (rmq_engine::FetchSlot& f : e->fslot)
-    if (f.ticket == ticket) {
-      HIP_TRY(hipSetDevice(e->device));
-      return fetch_slot_step(e, f, wait != 0, bytes_used);
-    }
-  for (auto it = e->fetch_done.begin(); it != e->fetch_done.end(); ++it)
-    if ((*it)[0] == ticket) {
-      const int rc = (int)(int64_t)(*it)[1];
-      if (bytes_used) *bytes_used = (*it)[2];
-      e->fetch_done.erase(it);
-      return rc;
-    }
-  return RMQ_EINVAL;
-}
-
-int rmq_fetch(rmq_engine* e, const rmq_fetch_req* reqs, uint32_t n, uint32_t mem, uint8_t* out,
-              uint64_t out_cap, rmq_fetch_res* res, uint64_t* bytes_used) {
-  if (bytes_used) *bytes_used = 0;
-  if (!e) return RMQ_EINVAL;
-  if (!n) return RMQ_OK;
-  uint64_t t = 0;
-  const int rc = fetch_issue(e, reqs, nullptr, nullptr, n, mem, out, out_cap, res, &t, true);
-  if (rc) return rc;
-  return rmq_fetch_poll(e, t, 1, bytes_used);
-}
-
-int rmq_fetch_bytes(rmq_engine* e, const rmq_fetch_req* reqs, const uint32_t* max_bytes, uint32_t n,
-                    uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* bytes_used) {
-  if (bytes_used) *bytes_used = 0;
-  if (!e) return RMQ_EINVAL;
-  if (!n) return RMQ_OK;
-  uint64_t t = 0;
-  const int rc = fetch_issue(e, reqs, nullptr, max_bytes, n, mem, out, out_cap, res, &t, true);
-  if (rc) return rc;
-  return rmq_fetch_poll(e, t, 1, bytes_used);
-}
-
-int rmq_fetch_at(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
-                 uint32_t n, uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res, uint64_t* bytes_used) {
-  if (bytes_used) *bytes_used = 0;
-  if (!e) return RMQ_EINVAL;
-  if (!n) return RMQ_OK;
-  uint64_t t = 0;
-  const int rc = fetch_issue(e, reqs, offsets, max_bytes, n, mem, out, out_cap, res, &t, true);
-  if (rc) return rc;
-  return rmq_fetch_poll(e, t, 1, bytes_used);
-}
-
-int rmq_fetch_table_async(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
-                          uint32_t n, uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res,
-                          uint64_t* rec_row, uint64_t* rec_pos, uint64_t rec_cap, uint64_t* ticket) {
-  return fetch_issue(e, reqs, offsets, max_bytes, n, mem, out, out_cap, res, ticket, false, rec_row, rec_pos, rec_cap);
-}
-
-int rmq_fetch_table(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, const uint32_t* max_bytes,
-                    uint32_t n, uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res,
-                    uint64_t* rec_row, uint64_t* rec_pos, uint64_t rec_cap, uint64_t* bytes_used) {
-  if (bytes_used) *bytes_used = 0;
-  if (!e) return RMQ_EINVAL;
-  if (!n && !rec_row && !rec_pos && !rec_cap) return RMQ_OK;  // (exactly rmq_fetch_at)
-  uint64_t t = 0;
-  const int rc = fetch_issue(e, reqs, offsets, max_bytes, n, mem, out, out_cap, res, &t, true, rec_row, rec_pos, rec_cap);
-  if (rc) return rc;
-  return rmq_fetch_poll(e, t, 1, bytes_used);
 }
 
 int rmq_get_partition_state(rmq_engine* e, uint32_t p, rmq_partition_state* o) {

@@ -1,6 +1,7 @@
 // engine_internal.hpp — the engine object shared by the host-side translation units
-// (engine.cpp: C-ABI, append pipeline, fetch, control; audit.cpp: scrub, repair, reindex, remote repair,
-// restore; replication.cpp: replica-log rounds; repair_remote.cpp: the rounds of rmq_repair_remote).
+// (engine.cpp: C-ABI, append pipeline, control; fetch.cpp: the fetch calls; audit.cpp: scrub, repair,
+// reindex, remote repair, restore; replication.cpp: replica-log rounds; repair_remote.cpp: the rounds of
+// rmq_repair_remote).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -596,7 +597,10 @@ int check_err(rmq_engine* e);
 int event_wait(hipEvent_t ev);  // spin on queries (20 ms), then block
 int stream_wait(hipStream_t s);  // the same for everything issued on a stream
 hipEvent_t pool_event(rmq_engine* e);
-int fetch_flush(rmq_engine* e);
+int late_retention(rmq_engine* e);  // the last applied group's retention, where its own launch stopped early
+// fetch.cpp
+int fetch_flush(rmq_engine* e);  // launch the asynchronous fetches held back (under mu)
+void fetch_free(rmq_engine* e);
 // The engine lock of every call: held-back asynchronous fetches go to the pipeline stream first, so
 // whatever the call issues is ordered after them (their contract); a launch error stays sticky on the
 // stream and surfaces at the next check.

@@ -431,6 +431,38 @@ class Engine:
             raise EngineError(rc, "rmq_poll_commit (offsets)")
         return rc
 
+    def _fetch_call(self, asyn: bool, req, n: int, mem: int, out, out_cap: int, res, last, at=None, bud=None, tab=None):
+        """One fetch through the narrowest C entry point that takes it, so that all ten stay in use:
+        rmq_fetch_table with a table (rec_row, rec_pos, rec_cap), else rmq_fetch_at with offsets, else
+        rmq_fetch_bytes with budgets, else rmq_fetch; asyn: its _async twin. Every array is an address
+        or None; last: the bytes_used / ticket word. Returns (rc, the entry point's name)."""
+        if tab is not None:
+            name, a = "rmq_fetch_table", (req, at, bud, n, mem, out, out_cap, res, *tab, last)
+        elif at is not None:
+            name, a = "rmq_fetch_at", (req, at, bud, n, mem, out, out_cap, res, last)
+        elif bud is not None:
+            name, a = "rmq_fetch_bytes", (req, bud, n, mem, out, out_cap, res, last)
+        else:
+            name, a = "rmq_fetch", (req, n, mem, out, out_cap, res, last)
+        if asyn:
+            name += "_async"
+        return getattr(self.lib, name)(self.h, *a), name
+
+    @staticmethod
+    def _fetch_rows(n: int, req, res, cols, flags: int = 0, fresh_flags: int = 0):
+        """The request and result rows of a call: the caller's arrays, or fresh zeroed ones (their
+        flags column then fresh_flags). cols = (pidx, consumer, max_records): None leaves that column
+        of req as it is; flags are ORed into every request."""
+        if req is None:
+            req = np.zeros((n, 4), np.uint32)
+            req[:, 3] = fresh_flags
+        if flags:
+            req[:, 3] |= flags
+        for col, v in enumerate(cols):
+            if v is not None:
+                req[:, col] = v
+        return req, np.zeros(n, FETCH_RES_DTYPE) if res is None else res
+
     def fetch(self, pidx, consumer, max_records, out_cap: int | None = None, commit: bool = False,
               out: np.ndarray | None = None, replica: bool = False, verify: bool = False, max_bytes=None,
               offsets=None, fill: bool = False, table=None):
@@ -450,53 +482,36 @@ class Engine:
         the call then returns (rc, res, out, bytes_used, rec_row, rec_pos), RMQ_ENOSPC also when
         rec_row[n] > rec_cap; table_records splits the output with it."""
         n = len(pidx)
-        tab = []  # the table's arrays, once the output's size is known (the size query takes none)
         if fill and out is None and out_cap is None:
             raise ValueError("fill needs out_cap or out: a filling fetch has no sizing call")
         bud = _budgets(max_bytes, n)
         at = _offsets(offsets, n)
-        host = A.RMQ_MEM_HOST | (A.RMQ_FETCH_FILL if fill else 0)
+        req, res = self._fetch_rows(n, None, None, (pidx, consumer, max_records),
+                                    (A.RMQ_FETCH_REPLICA if replica else 0) | (A.RMQ_FETCH_VERIFY if verify else 0))
+        used = C.c_uint64()
 
-        def call(*a):  # rmq_fetch, or rmq_fetch_bytes / rmq_fetch_at with their arrays after the requests
-            if tab:
-                return self.lib.rmq_fetch_table(a[0], a[1], _ptr(at), _ptr(bud), *a[2:7], _ptr(tab[0]), _ptr(tab[1]),
-                                                tab[2], a[7])
-            if at is not None:
-                return self.lib.rmq_fetch_at(a[0], a[1], _ptr(at), _ptr(bud), *a[2:])
-            if bud is None:
-                return self.lib.rmq_fetch(*a)
-            return self.lib.rmq_fetch_bytes(a[0], a[1], _ptr(bud), *a[2:])
+        def call(mem, out, cap, tab=None):
+            rc, _ = self._fetch_call(False, _ptr(req), n, mem, _ptr(out), cap, _ptr(res), C.byref(used), _ptr(at),
+                                     _ptr(bud), tab and (_ptr(tab[0]), _ptr(tab[1]), tab[2]))
+            if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
+                raise EngineError(rc, "rmq_fetch")
+            return rc
 
-        req = np.zeros((n, 4), np.uint32)
-        req[:, 0], req[:, 1], req[:, 2] = pidx, consumer, max_records
-        req[:, 3] = (A.RMQ_FETCH_REPLICA if replica else 0) | (A.RMQ_FETCH_VERIFY if verify else 0)
-        res = np.zeros(n, FETCH_RES_DTYPE)
+        ret = out  # (the caller's array as it came; a fresh one cut to out_cap)
         if out is not None:
-            if commit:
-                req[:, 3] |= A.RMQ_FETCH_COMMIT
-            used = C.c_uint64()
-            if table:
-                tab[:] = _host_table(table, n, out.size)
-            rc = call(self.h, _ptr(req), n, host, _ptr(out), out.size, _ptr(res), C.byref(used))
-            if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
-                raise EngineError(rc, "rmq_fetch")
-            return (rc, res, out, int(used.value)) + (tuple(tab[:2]) if table else ())
-        if out_cap is None:
-            used = C.c_uint64()
-            rc = call(self.h, _ptr(req), n, A.RMQ_MEM_HOST, None, 0, _ptr(res), C.byref(used))
-            if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
-                raise EngineError(rc, "rmq_fetch")
+            out_cap = out.size
+        elif out_cap is None:  # the size query: no flags of the call, no table, nothing committed
+            call(A.RMQ_MEM_HOST, None, 0)
             out_cap = int(used.value)
+        if out is None:
+            out = np.zeros(max(out_cap, 1), np.uint8)
+            ret = out[:out_cap]
         if commit:
             req[:, 3] |= A.RMQ_FETCH_COMMIT
-        out = np.zeros(max(out_cap, 1), np.uint8)
-        used = C.c_uint64()
-        if table:
-            tab[:] = _host_table(table, n, out_cap)
-        rc = call(self.h, _ptr(req), n, host, _ptr(out), out_cap, _ptr(res), C.byref(used))
-        if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
-            raise EngineError(rc, "rmq_fetch")
-        return (rc, res, out[:out_cap], int(used.value)) + (tuple(tab[:2]) if table else ())
+        # (the table's arrays once the output's size is known)
+        tab = _host_table(table, n, out_cap) if table else None
+        rc = call(A.RMQ_MEM_HOST | (A.RMQ_FETCH_FILL if fill else 0), out, out_cap, tab)
+        return (rc, res, ret, int(used.value)) + (tuple(tab[:2]) if table else ())
 
     def fetch_device(self, pidx, consumer, max_records, d_out: int, out_cap: int, commit: bool = False,
                      req: np.ndarray | None = None, res: np.ndarray | None = None, pinned_rows: bool = False,
@@ -516,55 +531,24 @@ class Engine:
         rec_cap 0: the size probe), with any kind of rows; the two addresses are then returned too."""
         tb = None if table is None else (C.c_void_p(table[0]), C.c_void_p(table[1] or None), int(table[2]))
         ret = () if table is None else (table[0], table[1])
+        used = C.c_uint64()
+        mem = A.RMQ_MEM_DEVICE | (A.RMQ_FETCH_FILL if fill else 0)
         if d_rows is not None:
-            n, d_req, d_res = d_rows[:3]
             if max_bytes is not None:
                 raise ValueError("device rows take their budgets as d_rows' fourth element")
-            used = C.c_uint64()
-            mem = A.RMQ_MEM_DEVICE | A.RMQ_FETCH_DEVICE_ROWS | (A.RMQ_FETCH_FILL if fill else 0)
-            if tb is not None:
-                rc = self.lib.rmq_fetch_table(self.h, C.c_void_p(d_req), C.c_void_p(None if offsets is None else int(offsets)),
-                                              C.c_void_p(d_rows[3] if len(d_rows) > 3 and d_rows[3] else None), n, mem,
-                                              d_out, out_cap, C.c_void_p(d_res), *tb, C.byref(used))
-            elif offsets is not None:
-                rc = self.lib.rmq_fetch_at(self.h, C.c_void_p(d_req), C.c_void_p(int(offsets)),
-                                           C.c_void_p(d_rows[3] if len(d_rows) > 3 and d_rows[3] else None), n, mem,
-                                           d_out, out_cap, C.c_void_p(d_res), C.byref(used))
-            elif len(d_rows) > 3 and d_rows[3]:
-                rc = self.lib.rmq_fetch_bytes(self.h, C.c_void_p(d_req), C.c_void_p(d_rows[3]), n, mem,
-                                              d_out, out_cap, C.c_void_p(d_res), C.byref(used))
-            else:
-                rc = self.lib.rmq_fetch(self.h, C.c_void_p(d_req), n, mem, d_out, out_cap, C.c_void_p(d_res),
-                                        C.byref(used))
-            if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
-                raise EngineError(rc, "rmq_fetch")
-            return (rc, None, int(used.value)) + ret
-        n = len(pidx) if pidx is not None else len(req)
-        if req is None:
-            req = np.zeros((n, 4), np.uint32)
-            req[:, 3] = A.RMQ_FETCH_COMMIT if commit else 0
-        if verify:
-            req[:, 3] |= A.RMQ_FETCH_VERIFY
-        for col, v in ((0, pidx), (1, consumer), (2, max_records)):
-            if v is not None:
-                req[:, col] = v
-        if res is None:
-            res = np.zeros(n, FETCH_RES_DTYPE)
-        used = C.c_uint64()
-        mem = A.RMQ_MEM_DEVICE | (A.RMQ_FETCH_PINNED_ROWS if pinned_rows else 0) | (A.RMQ_FETCH_FILL if fill else 0)
-        bud = _budgets(max_bytes, n)
-        at = _offsets(offsets, n)
-        if tb is not None:
-            rc = self.lib.rmq_fetch_table(self.h, _ptr_reused(req), _ptr(at), _ptr(bud), n, mem, d_out, out_cap,
-                                          _ptr_reused(res), *tb, C.byref(used))
-        elif at is not None:
-            rc = self.lib.rmq_fetch_at(self.h, _ptr_reused(req), _ptr(at), _ptr(bud), n, mem, d_out, out_cap,
-                                       _ptr_reused(res), C.byref(used))
-        elif bud is None:
-            rc = self.lib.rmq_fetch(self.h, _ptr_reused(req), n, mem, d_out, out_cap, _ptr_reused(res), C.byref(used))
+            n, res, mem = d_rows[0], None, mem | A.RMQ_FETCH_DEVICE_ROWS
+            p_req, p_res = C.c_void_p(d_rows[1]), C.c_void_p(d_rows[2])
+            p_at = None if offsets is None else C.c_void_p(int(offsets))
+            p_bud = C.c_void_p(d_rows[3]) if len(d_rows) > 3 and d_rows[3] else None
         else:
-            rc = self.lib.rmq_fetch_bytes(self.h, _ptr_reused(req), _ptr(bud), n, mem, d_out, out_cap,
-                                          _ptr_reused(res), C.byref(used))
+            n = len(pidx) if pidx is not None else len(req)
+            req, res = self._fetch_rows(n, req, res, (pidx, consumer, max_records), A.RMQ_FETCH_VERIFY if verify else 0,
+                                        A.RMQ_FETCH_COMMIT if commit else 0)
+            if pinned_rows:
+                mem |= A.RMQ_FETCH_PINNED_ROWS
+            bud, at = _budgets(max_bytes, n), _offsets(offsets, n)  # (alive until the call returns)
+            p_req, p_res, p_at, p_bud = _ptr_reused(req), _ptr_reused(res), _ptr(at), _ptr(bud)
+        rc, _ = self._fetch_call(False, p_req, n, mem, d_out, out_cap, p_res, C.byref(used), p_at, p_bud, tb)
         if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
             raise EngineError(rc, "rmq_fetch")
         return (rc, res, int(used.value)) + ret
@@ -590,16 +574,7 @@ class Engine:
         n = len(pidx) if pidx is not None else len(req)
         if pinned_rows and (req is None or res is None):
             raise ValueError("pinned_rows needs the caller's page-locked req and res (fetch_rows)")
-        if req is None:
-            req = np.empty((n, 4), np.uint32)
-            req[:, 3] = 0
-        if verify:
-            req[:, 3] |= A.RMQ_FETCH_VERIFY
-        for col, v in ((0, pidx), (1, consumer), (2, max_records)):
-            if v is not None:
-                req[:, col] = v
-        if res is None:
-            res = np.empty(n, FETCH_RES_DTYPE)
+        req, res = self._fetch_rows(n, req, res, (pidx, consumer, max_records), A.RMQ_FETCH_VERIFY if verify else 0)
         if d_out is not None:
             mem, ptr = A.RMQ_MEM_DEVICE, C.c_void_p(d_out)
         else:
@@ -612,6 +587,7 @@ class Engine:
         t = C.c_uint64()
         bud = _budgets(max_bytes, n)
         at = _offsets(offsets, n)
+        tb = None
         if table is not None and table is not False:
             if d_out is not None:
                 tb = (C.c_void_p(table[0]), C.c_void_p(table[1] or None), int(table[2]))
@@ -619,17 +595,8 @@ class Engine:
             else:
                 row, pos, cap = _host_table(table, n, out_cap)
                 tb, table = (_ptr(row), _ptr(pos), cap), (row, pos)
-            _check(self.lib.rmq_fetch_table_async(self.h, _ptr_reused(req), _ptr(at), _ptr(bud), n, mem, ptr, out_cap,
-                                                  _ptr_reused(res), *tb, C.byref(t)), "rmq_fetch_table_async")
-        elif at is not None:
-            _check(self.lib.rmq_fetch_at_async(self.h, _ptr_reused(req), _ptr(at), _ptr(bud), n, mem, ptr, out_cap,
-                                               _ptr_reused(res), C.byref(t)), "rmq_fetch_at_async")
-        elif bud is None:
-            _check(self.lib.rmq_fetch_async(self.h, _ptr_reused(req), n, mem, ptr, out_cap, _ptr_reused(res), C.byref(t)),
-                   "rmq_fetch_async")
-        else:
-            _check(self.lib.rmq_fetch_bytes_async(self.h, _ptr_reused(req), _ptr(bud), n, mem, ptr, out_cap,
-                                                  _ptr_reused(res), C.byref(t)), "rmq_fetch_bytes_async")
+        _check(*self._fetch_call(True, _ptr_reused(req), n, mem, ptr, out_cap, _ptr_reused(res), C.byref(t), _ptr(at),
+                                 _ptr(bud), tb))
         tk = FetchTicket(t.value, req, res, out, table or None)
         self._fetching[t.value] = tk
         return tk

@@ -73,7 +73,7 @@ def test_async_fetch_matches_sync_while_appending():
 
 def test_coalesced_async_fetches(oracle_mod):
     """Asynchronous fetches that commit nothing are held back and launched together, up to four
-    tickets in one resolve + gather pair (engine.cpp fetch_flush); a committing fetch, any other call,
+    tickets in one resolve + gather pair (fetch.cpp fetch_flush); a committing fetch, any other call,
     a fifth ticket or a poll launches the held ones first. Every ticket's results, bytes and the
     consumer table equal the oracle's, which runs the same calls one after the other."""
     P, C = 64, 4
