@@ -26,7 +26,7 @@ namespace {
 uint64_t audit_tasks(const rmq_engine* e, uint32_t first, uint32_t n) {
   uint64_t tasks = 0;
   for (uint32_t p = first; p < first + n; ++p)
-    tasks += e->cfg.replication_factor * (((1ull << (e->ring[p] & 63ull)) >> e->st.interval_log2) + 2ull);
+    tasks += e->cfg.replication_factor * ((ring_bytes(e->ring[p]) >> e->st.interval_log2) + 2ull);
   return tasks;
 }
 
@@ -38,8 +38,7 @@ int audit_begin(rmq_engine* e, uint32_t first, uint32_t n, bool* go, bool collec
   const uint32_t P = e->cfg.num_partitions;
   if (first > P || n > P - first) return RMQ_ENOPART;
   if (!n && !collective) return RMQ_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  const int rc = drain(e);
+  const int rc = begin_call(e, drain);
   *go = rc == RMQ_OK;
   return rc;
 }
@@ -109,11 +108,6 @@ struct ProfRegion {
     return rc ? rc : stream_wait(s);
   }
 };
-
-int read_words(std::vector<uint64_t>& h, const uint64_t* d) {
-  HIP_TRY(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost));
-  return RMQ_OK;
-}
 
 // A failure key is offset << 5 | slot << 2 | kind (kernels.hpp); rmq_restore's keys have no slot.
 uint64_t key_offset(uint64_t key) { return key >> 5; }
@@ -359,7 +353,7 @@ int rmq_restore(rmq_engine* e, uint32_t n, const rmq_restore_item* items, uint32
   if (rc) return rc;
   const RestorePlan pl = restore_plan(n, items, P, buf_bytes, rec_words, [&](uint32_t p) {
     RestorePart q;
-    q.seg = 1ull << (e->ring[p] & 63ull);
+    q.seg = ring_bytes(e->ring[p]);
     q.pristine = !(so[p] | sp[p] | eo[p] | ep[p]);
     q.local = false;
     for (uint32_t r = 0; r < RF; ++r) q.local = q.local || e->ranks[(size_t)p * RF + r] == e->cfg.rank;

@@ -11,8 +11,10 @@
 // append path: launch k reports launch k-1 complete through a host-visible word, and the tail is
 // read with hipStreamQuery. Control-plane calls (leadership, replicas, acks, consumer offsets,
 // fetch) flush and drain first and run synchronously: they are rare next to the append stream.
-// The fetch calls (their slots, staging and launches) are in fetch.cpp; the audit calls (scrub,
-// repair, reindex, remote repair, restore) are in audit.cpp.
+// This file keeps creation, the append pipeline, tickets, memory, profiling and transport attach. The
+// role and placement calls are in control.cpp, the read-backs and fault injection in inspect.cpp, the
+// fetch calls (their slots, staging and launches) in fetch.cpp and the audit calls (scrub, repair,
+// reindex, remote repair, restore) in audit.cpp.
 #include <chrono>
 
 #include "engine_internal.hpp"
@@ -913,326 +915,6 @@ int rmq_create(const rmq_config* cfg, rmq_engine** out) {
 
 void rmq_destroy(rmq_engine* e) { free_engine(e); }
 
-namespace {
-
-// Placement of n partitions (engine locked). With a replication transport this is collective:
-// every rank recomputes its out / in lists and checks them against its peers'.
-int set_placement(rmq_engine* e, uint32_t n, const uint32_t* pidx, const uint64_t* key, const uint32_t* ranks,
-                  const uint32_t* leader_slot) {
-  const uint32_t P = e->cfg.num_partitions, RF = e->cfg.replication_factor;
-  if (n && (!pidx || !ranks || !leader_slot)) return RMQ_EINVAL;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (pidx[i] >= P) return RMQ_ENOPART;
-    if (leader_slot[i] >= RF) return RMQ_EINVAL;
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = drain(e);
-  if (!rc) rc = equalize_state_sets(e);
-  if (rc) return rc;
-  std::vector<uint32_t> mask(P);
-  std::vector<uint32_t> demoted;  // partitions this engine stops leading
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t p = pidx[i];
-    for (uint32_t r = 0; r < RF; ++r) e->ranks[(size_t)p * RF + r] = ranks[(size_t)i * RF + r];
-    e->leader_slot[p] = leader_slot[i];
-    const uint32_t lead = ranks[(size_t)i * RF + leader_slot[i]] == e->cfg.rank;
-    if (e->is_leader[p] && !lead) demoted.push_back(p);
-    // a placement keeps or ends this replica's leadership; it never starts one: a replica the
-    // placement names leader leads once rmq_become_leader passes Raft's checks
-    e->is_leader[p] = lead && e->is_leader[p];
-    if (key) e->key[p] = key[i];
-  }
-  if (!demoted.empty()) {  // a former leader knows its own commit as the leader's (FORMAT.md §9 v4)
-    std::vector<uint64_t> c(P), lc(P);
-    HIP_TRY(hipMemcpy(c.data(), e->st.commit, P * 8ull, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(lc.data(), e->st.lcommit, P * 8ull, hipMemcpyDeviceToHost));
-    for (uint32_t p : demoted) lc[p] = std::max(lc[p], c[p]);
-    HIP_TRY(hipMemcpy(e->st.lcommit, lc.data(), P * 8ull, hipMemcpyHostToDevice));
-  }
-  for (uint32_t p = 0; p < P; ++p) {
-    mask[p] = 0;
-    for (uint32_t r = 0; r < RF; ++r) mask[p] |= (e->ranks[(size_t)p * RF + r] == e->cfg.rank ? 1u : 0u) << r;
-  }
-  HIP_TRY(hipMemcpy(e->st.is_leader, e->is_leader.data(), P * 4ull, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->st.local_mask, mask.data(), P * 4ull, hipMemcpyHostToDevice));
-  if (n) {  // the election timer of every placed partition restarts
-    std::vector<uint64_t> hd(P);
-    HIP_TRY(hipMemcpy(hd.data(), e->st.heard, P * 8ull, hipMemcpyDeviceToHost));
-    const uint64_t cur = e->repl ? e->repl->stamp : 0ull;
-    for (uint32_t i = 0; i < n; ++i) hd[pidx[i]] = cur;
-    HIP_TRY(hipMemcpy(e->st.heard, hd.data(), P * 8ull, hipMemcpyHostToDevice));
-    e->place_time = std::chrono::steady_clock::now();
-  }
-  return e->repl ? repl_set_lists(e) : RMQ_OK;
-}
-
-}  // namespace
-
-int rmq_set_replicas(rmq_engine* e, uint32_t pidx, const uint32_t* ranks, uint32_t rf, uint32_t leader_slot) {
-  if (!e) return RMQ_EINVAL;
-  EngineLock g(e);
-  if (pidx >= e->cfg.num_partitions) return RMQ_ENOPART;
-  if (!ranks || rf != e->cfg.replication_factor || leader_slot >= rf) return RMQ_EINVAL;
-  return set_placement(e, 1, &pidx, nullptr, ranks, &leader_slot);
-}
-
-int rmq_set_placement(rmq_engine* e, uint32_t n, const uint32_t* pidx, const uint64_t* key, const uint32_t* ranks,
-                      const uint32_t* leader_slot) {
-  if (!e) return RMQ_EINVAL;
-  EngineLock g(e);
-  return set_placement(e, n, pidx, key, ranks, leader_slot);
-}
-
-int rmq_become_leader(rmq_engine* e, uint32_t pidx, uint64_t term) {
-  if (!e) return RMQ_EINVAL;
-  EngineLock g(e);
-  const uint32_t P = e->cfg.num_partitions, RF = e->cfg.replication_factor;
-  if (pidx != RMQ_ALL_PARTITIONS && pidx >= P) return RMQ_ENOPART;
-  const uint32_t lo = pidx == RMQ_ALL_PARTITIONS ? 0 : pidx, hi = pidx == RMQ_ALL_PARTITIONS ? P : pidx + 1;
-  for (uint32_t p = lo; p < hi; ++p) {  // validate everything before changing anything
-    bool local = false;
-    for (uint32_t r = 0; r < RF; ++r) local |= e->ranks[(size_t)p * RF + r] == e->cfg.rank;
-    if (!local) return RMQ_EINVAL;
-    // with a transport the placement (collective) names the leader; this starts its term
-    if (e->repl && e->ranks[(size_t)p * RF + e->leader_slot[p]] != e->cfg.rank) return RMQ_EINVAL;
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = drain(e);
-  if (!rc) rc = equalize_state_sets(e);
-  if (rc) return rc;
-  // a follower adopts newer leader terms from replication rounds (FORMAT.md §9): the device holds
-  // the current terms
-  HIP_TRY(hipMemcpy(&e->term[lo], e->st.term + lo, (size_t)(hi - lo) * 8, hipMemcpyDeviceToHost));
-  for (uint32_t p = lo; p < hi; ++p) {
-    if (term < e->term[p]) return RMQ_EINVAL;
-    // one leader per term: not a term this replica led, nor one it gave its vote to another candidate
-    if (e->vterm[p] == term && (e->vled[p] || e->vfor[p] != e->cfg.rank)) return RMQ_ETERM;
-  }
-  {
-    // Raft's vote restriction, as far as this replica can tell: it may not lead a partition whose
-    // leader committed records its log does not verifiably hold (leader_commit from rounds and
-    // commit notices; verified: the whole log when it was matched in the current term, else the
-    // replica's own commit)
-    const size_t m = hi - lo;
-    std::vector<uint64_t> leo(m), lc(m), mt(m), cm(m);
-    HIP_TRY(hipMemcpy(leo.data(), e->st.leo + lo, m * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(lc.data(), e->st.lcommit + lo, m * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(mt.data(), e->st.mterm + lo, m * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(cm.data(), e->st.commit + lo, m * 8, hipMemcpyDeviceToHost));
-    for (uint32_t p = lo; p < hi; ++p) {
-      const size_t i = p - lo;
-      const uint64_t verified = mt[i] == e->term[p] ? leo[i] : cm[i];
-      if (verified < lc[i]) return RMQ_ESTALE;  // (a partition always led here: lc = 0)
-    }
-  }
-  for (uint32_t p = lo; p < hi; ++p) {
-    uint32_t slot = e->leader_slot[p];
-    if (!e->repl) {
-      slot = 0;
-      while (e->ranks[(size_t)p * RF + slot] != e->cfg.rank) ++slot;
-    }
-    e->leader_slot[p] = slot;
-    e->is_leader[p] = 1;
-    e->term[p] = term;
-    e->vterm[p] = term;  // a leader's vote is its own
-    e->vfor[p] = e->cfg.rank;
-    e->vled[p] = 1;
-  }
-  HIP_TRY(hipMemcpy(e->st.is_leader + lo, &e->is_leader[lo], (size_t)(hi - lo) * 4, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->st.term + lo, &e->term[lo], (size_t)(hi - lo) * 8, hipMemcpyHostToDevice));
-  launch_become_leader(e->st, pidx, e->main_s);
-  HIP_TRY(hipGetLastError());
-  rc = drain(e);
-  // Raft's leader start: nextIndex of every follower = the leader's last index + 1
-  if (!rc && e->repl) rc = reset_catchup(e);
-  return rc;
-}
-
-// Before a vote reads a partition's term and log: without a transport every batch submitted is
-// applied first (drain); with one, a flush would be collective (rmq_sync), so only what is issued is
-// waited for: the pipeline stream and the rounds' ingest on the exchange stream.
-static int vote_settle(rmq_engine* e) {
-  if (!e->repl) return drain(e);
-  int rc = quiesce(e);
-  if (rc) return rc;
-  HIP_TRY(hipStreamSynchronize(e->repl->xchg_s));
-  return RMQ_OK;
-}
-
-int rmq_vote(rmq_engine* e, uint32_t pidx, uint64_t term, uint32_t candidate, uint64_t cand_last_log_term,
-             uint64_t cand_log_end, uint32_t* granted) {
-  if (!e || !granted) return RMQ_EINVAL;
-  *granted = 0;
-  EngineLock g(e);
-  if (pidx >= e->cfg.num_partitions) return RMQ_ENOPART;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = vote_settle(e);
-  if (rc) return rc;
-  // with a transport nothing is flushed (a flush is collective): a leader of pidx whose groups in
-  // flight may still add its records answers RMQ_PENDING and changes nothing (a delayed RequestVote)
-  if (e->repl && e->is_leader[pidx] && (e->forming.nb || e->has1 || e->has2)) return RMQ_PENDING;
-  uint64_t cur = 0, lterm = 0, leo = 0;
-  HIP_TRY(hipMemcpy(&cur, e->st.term + pidx, 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&lterm, e->st.lterm + pidx, 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&leo, e->st.leo + pidx, 8, hipMemcpyDeviceToHost));
-  lterm &= ~kLtermBound;  // an unknown last log term: its upper bound (a stricter vote)
-  if (term < cur) return RMQ_OK;  // a candidate of an older term
-  if (term > cur) {  // Raft: a newer term is adopted; a leader steps down
-    e->term[pidx] = term;
-    HIP_TRY(hipMemcpy(e->st.term + pidx, &term, 8, hipMemcpyHostToDevice));
-    if (e->is_leader[pidx]) {
-      rc = equalize_state_sets(e);
-      if (rc) return rc;
-      uint64_t c = 0, lc = 0;
-      HIP_TRY(hipMemcpy(&c, e->st.commit + pidx, 8, hipMemcpyDeviceToHost));
-      HIP_TRY(hipMemcpy(&lc, e->st.lcommit + pidx, 8, hipMemcpyDeviceToHost));
-      if (c > lc) HIP_TRY(hipMemcpy(e->st.lcommit + pidx, &c, 8, hipMemcpyHostToDevice));  // (FORMAT.md §9 v4)
-      e->is_leader[pidx] = 0;
-      const uint32_t z = 0;
-      HIP_TRY(hipMemcpy(e->st.is_leader + pidx, &z, 4, hipMemcpyHostToDevice));
-    }
-  }
-  const bool up = cand_last_log_term > lterm || (cand_last_log_term == lterm && cand_log_end >= leo);
-  const bool free_vote = e->vterm[pidx] != term || (!e->vled[pidx] && e->vfor[pidx] == candidate);
-  if (up && free_vote) {
-    e->vterm[pidx] = term;
-    e->vfor[pidx] = candidate;
-    e->vled[pidx] = 0;
-    *granted = 1;
-  }
-  return RMQ_OK;
-}
-
-int rmq_set_vote(rmq_engine* e, uint32_t pidx, uint64_t term, uint32_t voted_for) {
-  if (!e) return RMQ_EINVAL;
-  EngineLock g(e);
-  if (pidx >= e->cfg.num_partitions) return RMQ_ENOPART;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = vote_settle(e);
-  if (rc) return rc;
-  uint64_t cur = 0;
-  HIP_TRY(hipMemcpy(&cur, e->st.term + pidx, 8, hipMemcpyDeviceToHost));
-  if (term > cur) {
-    e->term[pidx] = term;
-    HIP_TRY(hipMemcpy(e->st.term + pidx, &term, 8, hipMemcpyHostToDevice));
-  }
-  e->vterm[pidx] = term;
-  e->vfor[pidx] = voted_for;
-  e->vled[pidx] = 0;
-  return RMQ_OK;
-}
-
-int rmq_leader_silent(rmq_engine* e, uint32_t silent_rounds, uint32_t timeout_ms, uint32_t* out_pidx, uint32_t cap,
-                      uint32_t* n) {
-  if (!e || !n || (cap && !out_pidx)) return RMQ_EINVAL;
-  *n = 0;
-  EngineLock g(e);
-  const uint32_t P = e->cfg.num_partitions, RF = e->cfg.replication_factor;
-  HIP_TRY(hipSetDevice(e->device));
-  if (e->repl) HIP_TRY(hipStreamSynchronize(e->repl->xchg_s));  // (the rounds' ingest writes the words)
-  std::vector<uint64_t> hd(P);
-  HIP_TRY(hipMemcpy(hd.data(), e->st.heard, P * 8ull, hipMemcpyDeviceToHost));
-  const uint64_t cur = e->repl ? e->repl->stamp : 0ull;
-  const auto now = std::chrono::steady_clock::now();
-  uint32_t k = 0;
-  for (uint32_t p = 0; p < P; ++p) {
-    if (e->is_leader[p]) continue;
-    bool local = false;
-    for (uint32_t r = 0; r < RF; ++r) local |= e->ranks[(size_t)p * RF + r] == e->cfg.rank;
-    if (!local || hd[p] + silent_rounds > cur) continue;
-    // wall time since the leader was last heard (the round's posting, or the placement)
-    auto at = e->place_time;
-    if (e->repl && hd[p] && cur - hd[p] < 64) at = std::max(at, e->repl->stamp_time[hd[p] % 64]);
-    if (std::chrono::duration_cast<std::chrono::milliseconds>(now - at).count() < (long long)timeout_ms) continue;
-    if (k < cap) out_pidx[k] = p;
-    ++k;
-  }
-  *n = k;
-  return RMQ_OK;
-}
-
-int rmq_set_segments(rmq_engine* e, uint32_t n, const uint32_t* pidx, const uint64_t* seg) {
-  if (!e) return RMQ_EINVAL;
-  if (!n) return RMQ_OK;
-  if (!pidx || !seg) return RMQ_EINVAL;
-  std::lock_guard<std::mutex> fg(e->fetch_mu);  // no fetch reads a ring while it moves
-  EngineLock g(e);
-  const uint32_t P = e->cfg.num_partitions, ilog = e->st.interval_log2;
-  std::vector<uint8_t> seen(P, 0);
-  for (uint32_t i = 0; i < n; ++i) {
-    if (pidx[i] >= P) return RMQ_ENOPART;
-    if (seen[pidx[i]]++ || !is_pow2(seg[i]) || seg[i] < 4ull * e->cfg.index_interval || seg[i] > e->st.rstride)
-      return RMQ_EINVAL;
-  }
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = drain(e);
-  if (rc) return rc;
-  // (fetches run on the pipeline stream: the drain waited for them too)
-  // new rings first, all or nothing
-  std::vector<MigrateItem> items;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t p = pidx[i], lg = ilog2(seg[i]);
-    if ((e->ring[p] & 63ull) == lg) continue;
-    uint64_t off = 0;
-    if (!e->pool.alloc(lg, &off)) {
-      for (const MigrateItem& it : items) e->pool.release((uint32_t)(it.new_desc & 63ull), it.new_desc & ~63ull);
-      return RMQ_ENOMEM;
-    }
-    MigrateItem it{};
-    it.p = p;
-    it.old_desc = e->ring[p];
-    it.new_desc = off | lg;
-    items.push_back(it);
-  }
-  if (items.empty()) return RMQ_OK;
-  // retained range of every moved partition; a shrinking ring first applies retention at its new
-  // size (FORMAT.md §4: start = the first record at or after used - S', from the index)
-  std::vector<uint64_t> spos(P), soff(P), used(P);
-  HIP_TRY(hipMemcpy(spos.data(), e->st.start_pos, (size_t)P * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(soff.data(), e->st.start_off, (size_t)P * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(used.data(), e->st.used, (size_t)P * 8, hipMemcpyDeviceToHost));
-  for (MigrateItem& it : items) {
-    const uint64_t S1 = 1ull << (it.new_desc & 63ull);
-    const uint32_t p = it.p;
-    if (used[p] - spos[p] > S1) {
-      const uint64_t m = (used[p] - S1 + (1ull << ilog) - 1) >> ilog;
-      const RingRef o = ring_ref(it.old_desc, ilog, e->st.icap_mul);
-      uint64_t ent[2];
-      HIP_TRY(hipMemcpy(ent, e->st.index + (o.ibase + m % o.icap) * 2, 16, hipMemcpyDeviceToHost));
-      soff[p] = ent[0];
-      spos[p] = ent[1];
-    }
-    it.spos = spos[p];
-    it.soff = soff[p];
-    it.used = used[p];
-  }
-  uint32_t chunks = 0;  // workgroups of each move: its new ring in kMigrateChunk pieces
-  for (MigrateItem& it : items) {
-    it.chunk0 = chunks;
-    const uint64_t S1 = 1ull << (it.new_desc & 63ull);
-    chunks += (uint32_t)((S1 + kMigrateChunk - 1) / kMigrateChunk);
-  }
-  MigrateItem* d_items = nullptr;
-  rc = dalloc(&d_items, items.size());
-  if (!rc) {
-    HIP_TRY(hipMemcpy(d_items, items.data(), items.size() * sizeof(MigrateItem), hipMemcpyHostToDevice));
-    launch_migrate(e->st, d_items, (uint32_t)items.size(), chunks, e->main_s);
-    if (hipGetLastError() != hipSuccess) rc = RMQ_EDEVICE;
-  }
-  if (!rc) {
-    for (const MigrateItem& it : items) {
-      e->ring[it.p] = it.new_desc;
-      e->pool.release((uint32_t)(it.old_desc & 63ull), it.old_desc & ~63ull);
-    }
-    HIP_TRY(hipStreamSynchronize(e->main_s));
-    rc = check_err(e);
-  } else {
-    for (const MigrateItem& it : items) e->pool.release((uint32_t)(it.new_desc & 63ull), it.new_desc & ~63ull);
-  }
-  if (d_items) hipFree(d_items);
-  return rc;
-}
-
 int rmq_append(rmq_engine* e, const rmq_batch* b, uint64_t* out_offsets, uint64_t* ticket) {
   if (!e || !b || !ticket) return RMQ_EINVAL;
   EngineLock g(e);
@@ -1351,8 +1033,7 @@ int rmq_ack(rmq_engine* e, const uint32_t* pidx, const uint32_t* slot, const uin
     if (pidx[i] >= e->cfg.num_partitions) return RMQ_ENOPART;
     if (slot[i] >= e->cfg.replication_factor) return RMQ_EINVAL;
   }
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = drain(e);
+  int rc = begin_call(e, drain);
   if (rc) return rc;
   rc = ensure_ctl(e, n);
   if (rc) return rc;
@@ -1449,25 +1130,7 @@ int rmq_ticket_stats(rmq_engine* e, uint64_t ticket, rmq_append_stats* out) {
 int rmq_sync(rmq_engine* e) {
   if (!e) return RMQ_EINVAL;
   EngineLock g(e);
-  HIP_TRY(hipSetDevice(e->device));
-  return drain(e);
-}
-
-int rmq_set_replica_cursor(rmq_engine* e, uint32_t n, const uint32_t* pidx, const uint64_t* offset) {
-  if (!e || (n && (!pidx || !offset))) return RMQ_EINVAL;
-  EngineLock g(e);
-  const uint32_t P = e->cfg.num_partitions;
-  for (uint32_t i = 0; i < n; ++i)
-    if (pidx[i] >= P) return RMQ_ENOPART;
-  if (!n) return RMQ_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = quiesce(e);  // (fetches on the pipeline stream read and commit the cursors)
-  if (rc) return rc;
-  std::vector<uint64_t> cur(P);
-  HIP_TRY(hipMemcpy(cur.data(), e->st.rcur, P * 8ull, hipMemcpyDeviceToHost));
-  for (uint32_t i = 0; i < n; ++i) cur[pidx[i]] = offset[i];
-  HIP_TRY(hipMemcpy(e->st.rcur, cur.data(), P * 8ull, hipMemcpyHostToDevice));
-  return RMQ_OK;
+  return begin_call(e, drain);
 }
 
 int rmq_commit_consumer_offset(rmq_engine* e, const uint32_t* pidx, const uint32_t* consumer,
@@ -1580,198 +1243,6 @@ int rmq_commit_consumer_offset(rmq_engine* e, const uint32_t* pidx, const uint32
   return rc ? rc : rc_all;
 }
 
-int rmq_get_partition_state(rmq_engine* e, uint32_t p, rmq_partition_state* o) {
-  if (!e || !o) return RMQ_EINVAL;
-  EngineLock g(e);
-  if (p >= e->cfg.num_partitions) return RMQ_ENOPART;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = quiesce(e);
-  if (rc) return rc;
-  const DevState& s = e->st;
-  const uint32_t RF = e->cfg.replication_factor;
-  std::memset(o, 0, sizeof *o);
-  HIP_TRY(hipMemcpy(&o->log_end_offset, s.leo + p, 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&o->log_end_pos, s.used + p, 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&o->log_start_offset, s.start_off + p, 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&o->log_start_pos, s.start_pos + p, 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&o->commit, s.commit + p, 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&o->high_watermark, s.hw + p, 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&o->term_start, s.term_start + p, 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(o->match, s.match + (size_t)p * RF, RF * 8ull, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&o->term, s.term + p, 8, hipMemcpyDeviceToHost));
-  for (uint32_t r = 0; r < RF; ++r) o->replica_rank[r] = e->ranks[(size_t)p * RF + r];
-  o->leader_slot = e->leader_slot[p];
-  o->is_leader = e->is_leader[p];
-  o->segment_bytes = 1ull << (e->ring[p] & 63ull);
-  if (o->is_leader) o->leader_commit = o->commit;
-  else HIP_TRY(hipMemcpy(&o->leader_commit, s.lcommit + p, 8, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(&o->last_log_term, s.lterm + p, 8, hipMemcpyDeviceToHost));
-  if (o->last_log_term & kLtermBound) o->last_log_term = 0;  // unknown: a candidate claims none
-  HIP_TRY(hipMemcpy(&o->heard_round, s.heard + p, 8, hipMemcpyDeviceToHost));
-  o->voted_term = e->vterm[p];
-  o->voted_for = e->vfor[p];
-  o->led = e->vled[p];
-  return RMQ_OK;
-}
-
-int rmq_get_partition_states(rmq_engine* e, uint32_t first, uint32_t n, rmq_partition_state* o) {
-  if (!e || (n && !o)) return RMQ_EINVAL;
-  EngineLock g(e);
-  const uint32_t P = e->cfg.num_partitions, RF = e->cfg.replication_factor;
-  if (first > P || n > P - first) return RMQ_ENOPART;
-  if (!n) return RMQ_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = quiesce(e);
-  if (rc) return rc;
-  const DevState& s = e->st;
-  uint64_t* const src[] = {s.leo, s.used, s.start_off, s.start_pos, s.commit, s.hw, s.term, s.term_start, s.lcommit,
-                           s.lterm, s.heard};
-  constexpr int NF = sizeof src / sizeof src[0];
-  // every field gathered by one kernel into a page-locked staging area, one wait (12 synchronous
-  // copies into pageable vectors took 0.86 ms for 4,096 partitions)
-  const size_t words = (size_t)P * (NF + RF);
-  if (e->state_stage_words < words) {
-    if (e->state_stage) hipHostFree(e->state_stage);
-    e->state_stage = nullptr;
-    e->state_stage_words = 0;
-    HIP_TRY(hipHostMalloc((void**)&e->state_stage, words * 8, 0));
-    e->state_stage_words = words;
-  }
-  uint64_t* const v = e->state_stage;
-  uint64_t* const m = v + (size_t)n * NF;
-  static_assert(NF == 11, "state_gather_kernel's fields");
-  (void)src;
-  launch_state_gather(s, v, first, n, RF, e->main_s);  // (page-locked: the kernel writes it in place)
-  HIP_TRY(hipGetLastError());
-  rc = stream_wait(e->main_s);
-  if (rc) return rc;
-  for (uint32_t i = 0; i < n; ++i) {
-    const uint32_t p = first + i;
-    rmq_partition_state& x = o[i];
-    std::memset(&x, 0, sizeof x);
-    x.log_end_offset = v[i];
-    x.log_end_pos = v[(size_t)n + i];
-    x.log_start_offset = v[2ull * n + i];
-    x.log_start_pos = v[3ull * n + i];
-    x.commit = v[4ull * n + i];
-    x.high_watermark = v[5ull * n + i];
-    x.term = v[6ull * n + i];
-    x.term_start = v[7ull * n + i];
-    for (uint32_t r = 0; r < RF; ++r) {
-      x.match[r] = m[(size_t)i * RF + r];
-      x.replica_rank[r] = e->ranks[(size_t)p * RF + r];
-    }
-    x.leader_slot = e->leader_slot[p];
-    x.is_leader = e->is_leader[p];
-    x.segment_bytes = 1ull << (e->ring[p] & 63ull);
-    x.leader_commit = x.is_leader ? x.commit : v[8ull * n + i];
-    x.last_log_term = (v[9ull * n + i] & kLtermBound) ? 0ull : v[9ull * n + i];
-    x.heard_round = v[10ull * n + i];
-    x.voted_term = e->vterm[p];
-    x.voted_for = e->vfor[p];
-    x.led = e->vled[p];
-  }
-  return RMQ_OK;
-}
-
-int rmq_read_segment(rmq_engine* e, uint32_t replica, uint32_t p, uint64_t ring_off, uint64_t len, uint8_t* out) {
-  if (!e || (len && !out)) return RMQ_EINVAL;
-  EngineLock g(e);
-  if (p >= e->cfg.num_partitions) return RMQ_ENOPART;
-  const RingRef rg = ring_ref(e->ring[p], e->st.interval_log2, e->st.icap_mul);
-  if (replica >= e->cfg.replication_factor || ring_off > rg.seg || len > rg.seg - ring_off) return RMQ_EINVAL;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = quiesce(e);
-  if (rc) return rc;
-  if (len)
-    HIP_TRY(hipMemcpy(out, e->st.logs + (uint64_t)replica * e->st.rstride + rg.base + ring_off, len,
-                      hipMemcpyDeviceToHost));
-  return RMQ_OK;
-}
-
-int rmq_read_index(rmq_engine* e, uint32_t p, uint64_t m_first, uint64_t count, uint64_t* out) {
-  if (!e || (count && !out)) return RMQ_EINVAL;
-  EngineLock g(e);
-  if (p >= e->cfg.num_partitions) return RMQ_ENOPART;
-  const RingRef rg = ring_ref(e->ring[p], e->st.interval_log2, e->st.icap_mul);
-  const uint32_t icap = rg.icap;
-  if (count > icap) return RMQ_EINVAL;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = quiesce(e);
-  if (rc) return rc;
-  std::vector<uint64_t> ring((size_t)icap * 2);
-  HIP_TRY(hipMemcpy(ring.data(), e->st.index + rg.ibase * 2, ring.size() * 8, hipMemcpyDeviceToHost));
-  for (uint64_t k = 0; k < count; ++k) {
-    const uint64_t sl = (m_first + k) % icap;
-    out[2 * k] = ring[2 * sl];
-    out[2 * k + 1] = ring[2 * sl + 1];
-  }
-  return RMQ_OK;
-}
-
-int rmq_read_consumer_offsets(rmq_engine* e, uint32_t p, uint64_t* out) {
-  if (!e || !out) return RMQ_EINVAL;
-  EngineLock g(e);
-  if (p >= e->cfg.num_partitions) return RMQ_ENOPART;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = quiesce(e);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(out, e->st.cons + (size_t)p * e->cfg.max_consumers, e->cfg.max_consumers * 8ull,
-                    hipMemcpyDeviceToHost));
-  return RMQ_OK;
-}
-
-int rmq_read_consumer_table(rmq_engine* e, uint32_t first, uint32_t n, uint64_t* out) {
-  if (!e || (n && !out)) return RMQ_EINVAL;
-  EngineLock g(e);
-  if (first > e->cfg.num_partitions || n > e->cfg.num_partitions - first) return RMQ_ENOPART;
-  if (!n) return RMQ_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = quiesce(e);
-  if (rc) return rc;
-  const size_t C = e->cfg.max_consumers;
-  HIP_TRY(hipMemcpy(out, e->st.cons + (size_t)first * C, (size_t)n * C * 8, hipMemcpyDeviceToHost));
-  return RMQ_OK;
-}
-
-int rmq_fault_flip_ring(rmq_engine* e, uint32_t replica, uint32_t p, uint64_t ring_off, uint32_t xor_mask) {
-  if (!e) return RMQ_EINVAL;
-  EngineLock g(e);
-  if (p >= e->cfg.num_partitions) return RMQ_ENOPART;
-  const uint32_t RF = e->cfg.replication_factor;
-  const RingRef rg = ring_ref(e->ring[p], e->st.interval_log2, e->st.icap_mul);
-  if (replica >= RF || e->ranks[(size_t)p * RF + replica] != e->cfg.rank || ring_off >= rg.seg || !(xor_mask & 0xFFu))
-    return RMQ_EINVAL;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = drain(e);
-  if (rc) return rc;
-  // one byte inside the partition's own ring block of a local replica region
-  uint8_t* at = e->st.logs + (uint64_t)replica * e->st.rstride + rg.base + ring_off;
-  uint8_t b = 0;
-  HIP_TRY(hipMemcpy(&b, at, 1, hipMemcpyDeviceToHost));
-  b ^= (uint8_t)(xor_mask & 0xFFu);
-  HIP_TRY(hipMemcpy(at, &b, 1, hipMemcpyHostToDevice));
-  return RMQ_OK;
-}
-
-int rmq_fault_flip_index(rmq_engine* e, uint32_t pidx, uint64_t m, uint32_t word, uint64_t xor_mask) {
-  if (!e) return RMQ_EINVAL;
-  EngineLock g(e);
-  if (pidx >= e->cfg.num_partitions) return RMQ_ENOPART;
-  if (word > 1u || !xor_mask) return RMQ_EINVAL;
-  const RingRef rg = ring_ref(e->ring[pidx], e->st.interval_log2, e->st.icap_mul);
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = drain(e);
-  if (rc) return rc;
-  // one word of the partition's own index ring
-  uint64_t* at = e->st.index + (rg.ibase + m % rg.icap) * 2 + word;
-  uint64_t w = 0;
-  HIP_TRY(hipMemcpy(&w, at, 8, hipMemcpyDeviceToHost));
-  w ^= xor_mask;
-  HIP_TRY(hipMemcpy(at, &w, 8, hipMemcpyHostToDevice));
-  return RMQ_OK;
-}
-
 int rmq_device_alloc(rmq_engine* e, uint64_t bytes, void** out) {
   if (!e || !out) return RMQ_EINVAL;
   EngineLock g(e);
@@ -1784,8 +1255,7 @@ int rmq_device_alloc(rmq_engine* e, uint64_t bytes, void** out) {
 int rmq_device_free(rmq_engine* e, void* p) {
   if (!e) return RMQ_EINVAL;
   EngineLock g(e);
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = settle(e);
+  int rc = begin_call(e, settle);
   if (rc) return rc;
   if (p) HIP_TRY(hipFree(p));
   return RMQ_OK;
@@ -1807,8 +1277,7 @@ int rmq_memcpy(rmq_engine* e, void* dst, const void* src, uint64_t bytes, int ki
 int rmq_profile_enable(rmq_engine* e, int enable) {
   if (!e) return RMQ_EINVAL;
   EngineLock g(e);
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = settle(e);
+  int rc = begin_call(e, settle);
   if (rc) return rc;
   for (auto& v : e->prof) {
     for (EvPair& p : v) {
@@ -1831,8 +1300,7 @@ int rmq_profile_enable(rmq_engine* e, int enable) {
 int rmq_profile_query(rmq_engine* e, int kernel, uint64_t* launches, double* total_ms) {
   if (!e || kernel < 0 || kernel > 9) return RMQ_EINVAL;
   EngineLock g(e);
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = settle(e);
+  int rc = begin_call(e, settle);
   if (rc) return rc;
   if (kernel <= 1) {  // 0: pipeline launches in the region, 1: batches applied in it
     float ms = 0;
@@ -1868,8 +1336,7 @@ int rmq_attach_rccl(rmq_engine* e, const uint8_t* comm_id, uint32_t world) {
   if (!e || !comm_id || world < 2 || world > kMaxWorld) return RMQ_EINVAL;
   EngineLock g(e);
   if (e->repl) return RMQ_EINVAL;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = drain(e);
+  int rc = begin_call(e, drain);
   if (rc) return rc;
   Transport* t = make_rccl_transport(comm_id, world, e->cfg.rank);
   if (!t) return RMQ_EDEVICE;
@@ -1895,96 +1362,12 @@ int rmq_attach_local(rmq_engine* e, rmq_local_hub* h) {
   if (!e || !h) return RMQ_EINVAL;
   EngineLock g(e);
   if (e->repl) return RMQ_EINVAL;
-  HIP_TRY(hipSetDevice(e->device));
-  int rc = drain(e);
+  int rc = begin_call(e, drain);
   if (rc) return rc;
   Transport* t = make_local_transport(&h->hub, e->cfg.rank, e->device);
   rc = repl_attach(e, t);
   if (rc && !e->repl) delete t;
   return rc;
-}
-
-int rmq_replication_stats(rmq_engine* e, rmq_repl_stats* out) {
-  if (!e || !out) return RMQ_EINVAL;
-  EngineLock g(e);
-  std::memset(out, 0, sizeof *out);
-  if (!e->repl) return RMQ_OK;
-  const Replication* r = e->repl;
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipStreamSynchronize(r->xchg_s));
-  uint64_t c[7];
-  HIP_TRY(hipMemcpy(c, r->d_counters, sizeof c, hipMemcpyDeviceToHost));
-  out->world = r->world;
-  out->rank = r->rank;
-  out->out_entries = (uint32_t)r->xo_p.size();
-  out->in_entries = (uint32_t)r->xi_p.size();
-  out->rounds = r->rounds;
-  out->bytes_sent = r->bytes_sent;
-  out->bytes_received = r->bytes_recv;
-  out->records_ingested = c[0];
-  out->refused_crc = c[1];
-  out->refused_log = c[2];
-  out->bytes_ingested = c[3];
-  out->catchup_entries = c[4];
-  out->detached_plans = c[5];
-  out->general_plans = c[6];
-  out->host_waits = r->host_waits;
-  out->host_wait_ns = r->host_wait_ns;
-  return RMQ_OK;
-}
-
-int rmq_fault_drop_rounds(rmq_engine* e, uint32_t n) {
-  if (!e) return RMQ_EINVAL;
-  EngineLock g(e);
-  if (!e->repl) return RMQ_EINVAL;
-  e->repl->drop_from = e->last_ticket + 1;
-  e->repl->drop_n = n;
-  return RMQ_OK;
-}
-
-int rmq_fault_cut(rmq_engine* e, uint32_t dst, uint32_t n) {
-  int rc = rmq_fault_isolate(e, dst, n);
-  if (rc) return rc;
-  EngineLock g(e);
-  e->repl->cut_notice |= 1u << dst;
-  return RMQ_OK;
-}
-
-int rmq_fault_isolate(rmq_engine* e, uint32_t dst, uint32_t n) {
-  if (!e) return RMQ_EINVAL;
-  EngineLock g(e);
-  if (!e->repl || dst >= e->repl->world || dst == e->repl->rank) return RMQ_EINVAL;
-  e->repl->iso_from[dst] = e->last_ticket + 1;
-  e->repl->iso_n[dst] = n;
-  return RMQ_OK;
-}
-
-int rmq_fault_corrupt(rmq_engine* e, uint32_t dst, int64_t at) {
-  if (!e) return RMQ_EINVAL;
-  EngineLock g(e);
-  if (!e->repl || dst >= e->repl->world || dst == e->repl->rank) return RMQ_EINVAL;
-  e->repl->flip[dst] = true;
-  e->repl->flip_at[dst] = at;
-  return RMQ_OK;
-}
-
-int rmq_read_outbox(rmq_engine* e, uint32_t dst, uint8_t* out, uint64_t cap, uint64_t* size) {
-  if (!e || !size) return RMQ_EINVAL;
-  EngineLock g(e);
-  *size = 0;
-  Replication* r = e->repl;
-  if (!r || dst >= r->world) return RMQ_EINVAL;
-  if (r->last_set == ~0u) return RMQ_OK;
-  HIP_TRY(hipSetDevice(e->device));
-  HIP_TRY(hipStreamSynchronize(r->xchg_s));
-  const XchgSet& x = r->sets[r->last_set];
-  const uint64_t off = (uint64_t)dst * r->dcap;  // region d at d * dcap of the outbox
-  const uint64_t n = dst == r->rank ? 0 : x.h_sizes[2 * dst];
-  *size = n;
-  if (!out) return RMQ_OK;
-  if (n > cap) return RMQ_ENOSPC;
-  if (n) HIP_TRY(hipMemcpy(out, x.outbox + off, n, hipMemcpyDeviceToHost));
-  return RMQ_OK;
 }
 
 }  // extern "C"

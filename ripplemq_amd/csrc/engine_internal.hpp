@@ -1,7 +1,8 @@
 // engine_internal.hpp — the engine object shared by the host-side translation units
-// (engine.cpp: C-ABI, append pipeline, control; fetch.cpp: the fetch calls; audit.cpp: scrub, repair,
-// reindex, remote repair, restore; replication.cpp: replica-log rounds; repair_remote.cpp: the rounds of
-// rmq_repair_remote).
+// (engine.cpp: creation, append pipeline, tickets, memory and transport attach; control.cpp: roles,
+// placement, votes, ring moves; inspect.cpp: read-backs and fault injection; fetch.cpp: the fetch calls;
+// audit.cpp: scrub, repair, reindex, remote repair, restore; replication.cpp: replica-log rounds;
+// repair_remote.cpp: the rounds of rmq_repair_remote).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -589,10 +590,57 @@ int restore_grow(T** p, uint64_t* cap, uint64_t need) {
   return RMQ_OK;
 }
 
+// Synchronous typed copies between the host and device state: n words, or a whole host vector.
+template <typename T>
+int read_words(T* dst, const T* src, size_t n = 1) {
+  HIP_TRY(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyDeviceToHost));
+  return RMQ_OK;
+}
+template <typename T>
+int write_words(T* dst, const T* src, size_t n = 1) {
+  HIP_TRY(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+  return RMQ_OK;
+}
+template <typename T>
+int read_words(std::vector<T>& h, const T* d) { return read_words(h.data(), d, h.size()); }
+template <typename T>
+int write_words(T* d, const std::vector<T>& h) { return write_words(d, h.data(), h.size()); }
+
+// A ring descriptor (DevState::ring) taken apart on the host, next to kernels.hpp's ring_ref.
+inline uint64_t ring_bytes(uint64_t desc) { return 1ull << (desc & 63ull); }
+inline RingRef ring_of(const rmq_engine* e, uint32_t p) {
+  return ring_ref(e->ring[p], e->st.interval_log2, e->st.icap_mul);
+}
+inline void release_ring(rmq_engine* e, uint64_t desc) { e->pool.release((uint32_t)(desc & 63ull), desc & ~63ull); }
+
+// The placement's host mirror: the replica slots of partition p this rank holds (bit r: slot r, as
+// DevState::local_mask), whether it holds any, and the rank the placement names leader.
+inline uint32_t local_slots(const rmq_engine* e, uint32_t p) {
+  uint32_t mask = 0;
+  for (uint32_t r = 0; r < e->cfg.replication_factor; ++r)
+    mask |= (e->ranks[(size_t)p * e->cfg.replication_factor + r] == e->cfg.rank ? 1u : 0u) << r;
+  return mask;
+}
+inline bool is_local(const rmq_engine* e, uint32_t p) { return local_slots(e, p) != 0; }
+inline uint32_t leader_rank(const rmq_engine* e, uint32_t p) {
+  return e->ranks[(size_t)p * e->cfg.replication_factor + e->leader_slot[p]];
+}
+
+// The prologue of a call under the engine lock: this thread's device, then the pipeline as far as the
+// call needs it (drain, quiesce, settle or a wait of the caller's).
+inline int begin_call(rmq_engine* e, int (*wait)(rmq_engine*)) {
+  HIP_TRY(hipSetDevice(e->device));
+  return wait(e);
+}
+
 // engine.cpp
+bool is_pow2(uint64_t v);
+uint32_t ilog2(uint64_t v);
 int flush(rmq_engine* e);
 int drain(rmq_engine* e);
 int quiesce(rmq_engine* e);
+int settle(rmq_engine* e);  // drain, or with a transport (where a flush is collective) quiesce
+int equalize_state_sets(rmq_engine* e);  // both state sets hold every log end (drained; before a role changes)
 int check_err(rmq_engine* e);
 int event_wait(hipEvent_t ev);  // spin on queries (20 ms), then block
 int stream_wait(hipStream_t s);  // the same for everything issued on a stream

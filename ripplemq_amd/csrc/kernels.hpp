@@ -1,4 +1,4 @@
-// kernels.hpp — launch interface between the host engine (engine.cpp) and the gfx950 kernels.
+// kernels.hpp — launch interface between the host engine (the .cpp files) and the gfx950 kernels.
 // Plain structs of device pointers; no torch types, no host STL.
 #pragma once
 #include <hip/hip_runtime.h>
