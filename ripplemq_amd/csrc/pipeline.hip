@@ -1150,7 +1150,7 @@ __device__ __forceinline__ void flag_no_space(u64* ecol, u32 s, u32 t0, u32 t1) 
 // Column p's batch scans when some cell of the wave's columns is kCellWide (a tile run of more than
 // kCellB16 16-byte units, i.e. records averaging over 32 KB) or the group spans more than one chunk
 // of kScanLanes * kCL tiles: the same scans as stage2_column, the cells read from memory one by one.
-// Returns the group aggregate over accepted cells.
+// Returns the group aggregate over accepted cells; every batch's bcum row is written here.
 __device__ __attribute__((noinline)) u64 stage2_column_general(const PipeArgs& A, u32 p, u32 s, u32 rm) {
   const PipeGroup& G = A.g2;
   const PipeScratch& x = A.s2;
@@ -1193,6 +1193,10 @@ __device__ __attribute__((noinline)) u64 stage2_column_general(const PipeArgs& A
       if (s == 0) x.bcum[(u64)j * P + p] = carry;
     }
   }
+  // batches without tiles at the end of a group whose tiles end on a chunk boundary: the loop
+  // above never reaches them (tile0[j] == T == C), and their rows still hold an earlier group's
+  for (; j < G.nb; ++j)
+    if (s == 0) x.bcum[(u64)j * P + p] = carry;
   return carry;
 }
 
