@@ -261,7 +261,7 @@ struct PipeArgs {
   PipeScratch s1, s2, s3, s4;
   uint32_t wg1, wg2, wgp, wg3;  // workgroups per role, in this order along blockIdx.x
   uint32_t wgb;                 // stage 3's large-record workgroups (last along blockIdx.x)
-  uint32_t key_passes;     // 1 (P <= 256) or 2
+  uint32_t key_passes;     // 8-bit radix passes of stage 1's sort: 0 (P == 1: no sort), 1 (P <= 256) or 2
   uint32_t key_bits;       // bits of the largest partition id (P - 1)
   uint32_t rank_mode;      // stage 1: 0 LDS radix sort + segmented scan, 1 wave-ordered hash counters
   uint32_t gt;             // tiles per hist / excl column (group tile capacity)

@@ -56,11 +56,12 @@
 namespace RMQ_PIPE_NS {
 using namespace rmq;
 
-constexpr u32 kPT = kPipeThreads;   // 512 (RMQ_PIPE_THREADS)
-constexpr u32 kPW = kPT / 64;       // 8 waves
+// (single-GPU kernel / kernel with a transport)
+constexpr u32 kPT = kPipeThreads;   // 256 / 512 threads (RMQ_PIPE_THREADS)
+constexpr u32 kPW = kPT / 64;       // 4 / 8 waves
 constexpr u32 kTR = kTileRecs;      // 1024
-constexpr u32 kTI = kTR / kPT;      // 2 records per thread in stage 1
-constexpr u32 kWR = kTR / kPW;      // 128 records per wave in stage 1
+constexpr u32 kTI = kTR / kPT;      // 4 / 2 records per thread in stage 1
+constexpr u32 kWR = kTR / kPW;      // 256 / 128 records per wave in stage 1
 constexpr u32 kIB = kTileIdxBits;   // 10
 constexpr u32 kFlagShift = 29;
 constexpr u32 kRankMask = (1u << kFlagShift) - 1u;
@@ -199,7 +200,7 @@ __device__ __forceinline__ void stage1_tile(const PipeArgs& A, u32 t, Stage1Smem
   const u32 nin = b.n - base < kTR ? b.n - base : kTR;
   PIPE_STAMP_ROW(srow, 0);
 
-  // ---- loads (input position q = 128w + 64r + lane)
+  // ---- loads (input position q = kWR w + 64 r + lane)
   u32 item[kTI], lenv[kTI], fl[kTI];
   u32 pc[kTI];
 #pragma unroll
