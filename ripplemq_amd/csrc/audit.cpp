@@ -11,12 +11,18 @@ using namespace rmq;
 
 namespace rmq {
 
+// Everything the audit calls grew: rmq_engine::Audit and rmq_restore's rmq_engine::Restore.
 void audit_free(rmq_engine* e) {
   rmq_engine::Audit& B = e->au;
   void* bufs[] = {B.tbase, B.rows, B.verdict, B.counts, B.gaps, B.scratch, B.rcounts};
   for (void* p : bufs)
     if (p) hipFree(p);
   B = rmq_engine::Audit();
+  rmq_engine::Restore& R = e->rs;
+  void* rbufs[] = {R.buf, R.tab, R.items, R.rbase, R.key};
+  for (void* p : rbufs)
+    if (p) hipFree(p);
+  R = rmq_engine::Restore();
 }
 
 namespace {

@@ -1,8 +1,10 @@
 // engine_internal.hpp — the engine object shared by the host-side translation units
-// (engine.cpp: creation, append pipeline, tickets, memory and transport attach; control.cpp: roles,
+// (engine.cpp: creation, destruction, memory, profiling and transport attach; append.cpp: the append
+// pipeline and its tickets; offsets.cpp: consumer-offset commits and acks; control.cpp: roles,
 // placement, votes, ring moves; inspect.cpp: read-backs and fault injection; fetch.cpp: the fetch calls;
 // audit.cpp: scrub, repair, reindex, remote repair, restore; replication.cpp: replica-log rounds;
-// repair_remote.cpp: the rounds of rmq_repair_remote).
+// repair_remote.cpp: the rounds of rmq_repair_remote). launch_plan.hpp holds the knobs and the role
+// grid of a launch, free of the device runtime.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +26,7 @@
 #include "../../include/ripplemq_engine.h"
 #include "device_common.hpp"
 #include "kernels.hpp"
+#include "launch_plan.hpp"
 #include "transport.hpp"
 
 using namespace rmq;
@@ -272,46 +275,58 @@ struct rmq_engine {
   std::mutex mu;
   int device = 0;
   uint32_t cu_count = 0;
-  uint32_t verify_wgs = 0;  // follower verify grid (RMQ_VERIFY_WGS; default 4 workgroups per CU)
-  uint32_t audit_wgs = 0;   // scrub verify and fetch verify grids at most (RMQ_AUDIT_WGS; 0: 8 workgroups per CU)
   char dev_name[256] = {0};
-  hipStream_t main_s = nullptr;
+
+  // ---- knobs: read from the environment by rmq_create, never afterwards (launch_plan.hpp)
+  rmq::Knobs knob;
+
+  // ---- streams and events
+  hipStream_t main_s = nullptr;  // the pipeline stream
+  hipStream_t rank_s = nullptr;  // the ranking launches of split launches (Knobs::split)
+  hipStream_t copy_s = nullptr;  // host batches and fetch requests: pinned -> device DMA
+  hipStream_t fetch_out_s = nullptr;  // fetch results (and host outputs) -> host, after the kernels:
+                                      // a fetch's result copy overlaps the next fetch's kernels
+  hipEvent_t ev_main = nullptr;
+  hipEvent_t ev_rank[2] = {nullptr, nullptr};  // rank launch L recorded in slot L & 1
+  hipEvent_t ev_pre_rank = nullptr;            // main_s before a rank launch
+  uint64_t rank_seq = 0;        // the last launch that had a rank launch (0: none)
+  std::vector<hipEvent_t> ev_pool;
+
+  // ---- device state
   DevState st{};            // leo/used point at sets[applied & 1]
   StateSet sets[2]{};
   uint64_t applied = 0;     // stage-3 launches issued
   CrcConsts* d_crc = nullptr;
   uint32_t* d_rlate = nullptr;  // [P] partitions whose retention of the applied group stopped early
   uint4* d_stats = nullptr;  // [kStatsRing][max tasks]
+  PipeScratch scratch[kSets]{};
   rmq::SegPool pool;         // ring space of each replica region
-  std::vector<uint64_t> ring;  // [P] host copy of DevState::ring
+  // device and page-locked memory that lives as long as the engine, recorded where it is allocated
+  // (owned_dalloc, owned_host_alloc) and freed from these lists alone
+  std::vector<void*> owned_dev, owned_host;
+
+  // ---- pipeline groups and launch counters: the group being formed, then groups ranked (need
+  // stage 2), scanned (need stage 3) and applied (need stage 4)
+  GroupFlight forming, g1, g2, g3;
+  bool has1 = false, has2 = false, has3 = false;
+  uint64_t g3_seq = 0;     // the launch that applied g3 (its retention is late if done_host[1] >= it)
+  uint64_t late_done = 0;  // the applied group (by launch) whose late retention ran (late_retention)
+  uint32_t set_reset = 0;  // scratch sets whose large-record list and batch sums the next stage 1 zeroes
+  uint32_t group_max = 2;       // batches per group (cfg.pipeline_depth)
+  uint32_t max_group_tiles = 0;
   uint32_t max_tasks = 0;
   uint32_t max_tiles = 0;
   uint32_t key_passes = 0;
   uint32_t key_bits = 0;
-  uint32_t rank_mode = 0;  // RMQ_RANK: stage 1 by the LDS radix sort (0) or by hash counters (1;
-                           // 4.86 vs 5.14 G msgs/s at config B, profiles/r04c_*)
-  uint32_t max_ahead = 0;  // RMQ_AHEAD: pipeline launches queued at most (0: unbounded; a bound of
-                           // 4 or 8 cost 4-6 % at config B, profiles/r04i_*: bound it in the app)
-  uint32_t steal = 0;      // RMQ_STEAL=1: stage-3 workgroups take stage-1 tiles when out of tasks
-  uint32_t prio = 1;  // RMQ_PRIO (round 6 default 1; 0 off): stage-1/2 and partition waves at s_setprio 3
-                           // (5.20 -> 4.00 G msgs/s: stage 2 and the second half of stage 3 start later)
-  PipeScratch scratch[kSets]{};
-  std::vector<Staging> staging;
-  CopyPool* copy_pool = nullptr;  // host batches (created with the first one)
-  uint32_t big_wgs = 0;           // stage-3 workgroups for records over 1 KB (RMQ_BIG_WGS; 0: 32 waves per CU)
-  // pipeline: the group being formed, then groups ranked (need stage 2), scanned (need stage 3)
-  // and applied (need stage 4)
-  GroupFlight forming, g1, g2, g3;
-  bool has1 = false, has2 = false, has3 = false;
-  uint64_t g3_seq = 0;
-  uint32_t set_reset = 0;  // scratch sets whose large-record list and batch sums the next stage 1 zeroes  // the launch that applied g3 (its retention is late if done_host[1] >= it)
-  uint32_t group_max = 2;       // batches per group (cfg.pipeline_depth)
-  uint32_t max_group_tiles = 0;
   uint64_t groups = 0;          // groups formed
   uint64_t launch_seq = 0;
   uint64_t* done_host = nullptr;     // pinned: [0] launch k-1 complete, written by launch k;
                                      // [1] the last launch whose retention stopped early
   uint64_t* done_dev = nullptr;
+  std::vector<Staging> staging;   // host batches: a slot per batch of the forming group and of three in flight
+  CopyPool* copy_pool = nullptr;  // host batches (created with the first one)
+
+  // ---- tickets
   uint64_t last_ticket = 0;
   std::vector<uint32_t> ticket_n;        // [kStatsRing] records of each recent ticket (stats)
   // completion: tickets are applied in order, launch after launch. marks = {hi, L}: every ticket
@@ -319,7 +334,10 @@ struct rmq_engine {
   // non-empty one before them); every ticket <= done_ticket is complete.
   std::deque<std::pair<uint64_t, uint64_t>> marks;
   uint64_t done_ticket = 0;
-  // host mirrors of control state
+
+  // ---- host mirrors of control state
+  std::vector<uint64_t> ring;  // [P] host copy of DevState::ring
+  std::vector<uint64_t> key;   // [P] placement key of each partition (FORMAT.md §9 list order)
   std::vector<uint32_t> is_leader, leader_slot, ranks;  // ranks [P][RF]
   std::vector<uint64_t> term;
   // votes (Raft's votedFor per term, raft_meta): the term of the last vote, the candidate, and whether
@@ -327,14 +345,11 @@ struct rmq_engine {
   std::vector<uint64_t> vterm;
   std::vector<uint32_t> vfor, vled;
   std::chrono::steady_clock::time_point place_time = std::chrono::steady_clock::now();  // last placement
-  // fetch: its own stream and scratch, serialised by fetch_mu (engine state under mu only while
+  rmq::Replication* repl = nullptr;  // replication transport attached (collective mode)
+
+  // ---- fetch: its own stream and scratch, serialised by fetch_mu (engine state under mu only while
   // the fetch is ordered against the pipeline stream)
   std::mutex fetch_mu;
-  hipStream_t fetch_out_s = nullptr;  // fetch results (and host outputs) -> host, after the kernels:
-                                      // a fetch's result copy overlaps the next fetch's kernels
-  hipStream_t copy_s = nullptr;  // host batches and fetch requests: pinned -> device DMA
-  hipEvent_t ev_main = nullptr;
-  bool trace = false;           // RMQ_TRACE: print every launch's roles to stderr
   // fetches in flight (rmq_fetch_async), each with its own scratch: a fetch is ordered after the
   // launches issued before it and before the ones issued after it; the host only waits in
   // rmq_fetch_poll (or when every slot is taken: the oldest is completed into its caller's arrays
@@ -399,7 +414,9 @@ struct rmq_engine {
   std::vector<uint32_t> fetch_stamp_rep;  // the same for replica reads ([P]: one replica cursor each)
   uint32_t fetch_gen = 0;
   std::deque<std::array<uint64_t, 3>> fetch_done;  // {ticket, rc, bytes used} completed, not yet polled
-  // consumer-offset commits: staging slots (pinned items -> device by one copy on the pipeline
+  std::vector<uint32_t> fpend;  // slots of asynchronous fetches whose kernels wait for fetch_flush (under mu)
+
+  // ---- consumer commits: staging slots (pinned items -> device by one copy on the pipeline
   // stream), so a commit is ordered with the append stream without waiting for it
   struct CommitSlot {
     uint8_t* h = nullptr;
@@ -423,20 +440,27 @@ struct rmq_engine {
   uint64_t off_ticket_seq = 0;
   std::deque<std::pair<uint64_t, std::vector<std::pair<uint32_t, uint64_t>>>> off_tickets;
   static constexpr size_t kMaxOffsetTickets = 256;   // the newest unpolled ones are kept
-  // ack scratch
-  uint32_t* d_ctl32 = nullptr;
-  uint64_t* d_ctl64 = nullptr;
-  uint32_t ctl_cap = 0;
-  // profiling: pipeline launches are timed as one region (event before the first launch after
+
+  // ---- profile: pipeline launches are timed as one region (event before the first launch after
   // enable, event at the next drain) so no per-launch events sit between kernels; fetch kernels
   // keep per-launch event pairs (prof[3], prof[4]), and so do every rmq_scrub (prof[2]), every rmq_repair (prof[5]), every rmq_repair_remote (prof[6]), every rmq_restore (prof[7]), every rmq_reindex (prof[8]) and every fetch's record-table kernels (prof[9])
   uint32_t profile = 0;
   uint32_t fetch_replay = 1;     // rmq_profile_enable(k >= 2): each fetch's kernels run k times
   uint64_t prof_fetch_runs = 0;
-  uint64_t prof_launches = 0, prof_batches = 0;
-  hipEvent_t prof_t0 = nullptr, prof_t1 = nullptr;
-  bool prof_started = false, prof_ended = false;
+  struct ProfRegion {
+    uint64_t launches = 0, batches = 0;
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    bool started = false, ended = false;
+  } region;
   std::vector<EvPair> prof[10];
+
+  // ---- per-subsystem scratch, grown on demand and freed by its subsystem
+  // ack scratch (offsets.cpp)
+  uint32_t* d_ctl32 = nullptr;
+  uint64_t* d_ctl64 = nullptr;
+  uint32_t ctl_cap = 0;
+  uint64_t* state_stage = nullptr;  // page-locked staging of rmq_get_partition_states
+  size_t state_stage_words = 0;
   // rmq_scrub, rmq_repair, rmq_repair_remote, rmq_reindex (audit.cpp): device buffers of one call's
   // range of n partitions, grown on demand (a capacity in elements next to each)
   struct Audit {
@@ -482,54 +506,11 @@ struct rmq_engine {
     uint64_t* key = nullptr;     // [items]
     uint64_t buf_cap = 0, tab_cap = 0, items_cap = 0;
   } rs;
-  uint64_t repair_peer_bytes = 64ull << 20;  // RMQ_REPAIR_PEER_BYTES: segment bytes asked of one rank per round (a capacity)
-  std::vector<hipEvent_t> ev_pool;
-  // diagnostics: RMQ_STAMPS=<csv> records per-wave phase stamps of launch RMQ_STAMPS_AT (default 100)
+
+  // ---- diagnostics: RMQ_STAMPS=<csv> records per-wave phase stamps of launch RMQ_STAMPS_AT (default 100)
   const char* stamps_path = nullptr;
-  uint64_t stamps_at = 100;
   uint64_t* d_stamps = nullptr;
-  uint32_t stamps_wg[5] = {0, 0, 0, 0, 0};  // roles of the stamped launch: s1, s2, parts, s3, s3 lead
-  // one stage-3 wave per task: the workgroups beyond the resident slots dispatch as stage-1/2
-  // workgroups retire (RMQ_WG3_ALL=0: only as many as fit next to them, looping over tasks)
-  uint32_t wg3_all = 1;
-  uint32_t s1_wgs = 0;    // RMQ_S1_WGS: stage-1 workgroups per launch (0: one per tile; fewer loop over tiles)
-  uint32_t s2_wgs = 0;    // RMQ_S2_WGS: cap on stage-2 workgroups (0: one thread group per column)
-  uint32_t s3_first = 0;  // RMQ_S3_FIRST=1: stage-3 workgroups first in dispatch order (round 6 default: last, -2.5 %)
-  uint32_t s3_lead = 0;   // stage-3 workgroups before the other roles (RMQ_S3_LEAD; 0: all of them)
-  uint32_t debug = 0;  // RMQ_DEBUG (timing experiments only; results are invalid when set)
-  // Split launches (single-GPU kernel, no transport): each pipeline step is two launches of the
-  // pipeline kernel that run side by side, the ranking roles (stage 1 of group g, stage 2 of g - 1)
-  // on rank_s and the apply roles (stage 3 of g - 2, partition threads, stage 4) on main_s. Rank
-  // launch L waits for everything main_s issued before it (apply L - 1 resets the set stage 1 of L
-  // reuses); apply launch L waits for rank launch L - 1 (the scans of the group it applies).
-  // RMQ_SPLIT=1 (2: the two launches one after the other, timing only); 0 default: one launch per
-  // step with every role (the split measured slower: 60 vs 49 us per step).
-  uint32_t split = 0;
-  uint32_t rank_cus = 0;        // RMQ_RANK_CUS=n: rank_s runs on n CUs and main_s on the others
-  uint64_t* state_stage = nullptr;  // page-locked staging of rmq_get_partition_states
-  size_t state_stage_words = 0;
-  uint32_t s3_pair = 0;         // RMQ_S3_PAIR=1: stage-3 waves take two tasks each (single-GPU kernel)
-  uint64_t late_done = 0;       // the applied group (by launch) whose late retention ran (late_retention)
-  std::vector<uint32_t> fpend;  // slots of asynchronous fetches whose kernels wait for fetch_flush (under mu)
-  uint32_t fetch_coalesce = kFetchBatch;  // RMQ_FETCH_COALESCE: asynchronous fetches launched together (1: none)
-  uint32_t s3_stage = 1;        // RMQ_S3_STAGE (default 1): stage-3 payload spans by coalesced loads through LDS
-  uint32_t s3_roles = 0;        // RMQ_S3_ROLES=k: stage 3 in loader / storer waves, k workgroups per CU (single-GPU kernel)
-  uint32_t s3_xcd = 1;          // RMQ_S3_XCD (default 1): stage-3 tasks in contiguous ranges per XCD
-                                //   (blockIdx % 8); round 5: 5.51-5.58 vs 5.43-5.51 G, 3 pairs, r05X8
-  uint32_t s1_xcd = 0;          // RMQ_S1_XCD=1: stage-1 tiles in contiguous ranges per XCD
-  // RMQ_FETCH_DMA: host request / result rows of a fetch moved by DMA (request rows on copy_s before
-  // the kernels, result rows on fetch_out_s after them) instead of read and written in place by
-  // the kernels across PCIe: 0 never (default), 1 for rmq_fetch_async, 2 for every fetch. Measured
-  // (round 5, tools/exp_dma.sh): the kernels gain 4-11 us but each fetch's copies and cross-stream
-  // waits add ~100 us (max = 10 bursts 3.3 -> 1.1 G records/s), so in place stays the default
-  uint32_t fetch_dma = 0;
-  uint32_t fetch_dma_in = 1;    // RMQ_FETCH_DMA_IN=0: with DMA, the request rows still read in place
-  hipStream_t rank_s = nullptr;
-  hipEvent_t ev_rank[2] = {nullptr, nullptr};  // rank launch L recorded in slot L & 1
-  hipEvent_t ev_pre_rank = nullptr;            // main_s before a rank launch
-  uint64_t rank_seq = 0;        // the last launch that had a rank launch (0: none)
-  std::vector<uint64_t> key;  // [P] placement key of each partition (FORMAT.md §9 list order)
-  rmq::Replication* repl = nullptr;  // replication transport attached (collective mode)
+  rmq::RolePlan stamps_plan;  // the roles of the stamped launch
 };
 
 namespace rmq {
@@ -570,6 +551,22 @@ int grow(T** p, uint64_t* cap, uint64_t need) {
   int rc = dalloc(p, (size_t)need);
   if (rc) return rc;
   *cap = need;
+  return RMQ_OK;
+}
+
+// Memory that lives as long as the engine: recorded where it is allocated, freed by free_engine from
+// the lists alone (a buffer whose zeroing failed is recorded too).
+template <typename T>
+int owned_dalloc(rmq_engine* e, T** p, size_t count) {
+  const int rc = dalloc(p, count);
+  if (*p) e->owned_dev.push_back(*p);
+  return rc;
+}
+template <typename T>
+int owned_host_alloc(rmq_engine* e, T** p, size_t bytes, unsigned flags) {
+  *p = nullptr;
+  HIP_TRY(hipHostMalloc((void**)p, bytes, flags));
+  e->owned_host.push_back(*p);
   return RMQ_OK;
 }
 
@@ -636,16 +633,22 @@ inline int begin_call(rmq_engine* e, int (*wait)(rmq_engine*)) {
 // engine.cpp
 bool is_pow2(uint64_t v);
 uint32_t ilog2(uint64_t v);
-int flush(rmq_engine* e);
-int drain(rmq_engine* e);
-int quiesce(rmq_engine* e);
-int settle(rmq_engine* e);  // drain, or with a transport (where a flush is collective) quiesce
 int equalize_state_sets(rmq_engine* e);  // both state sets hold every log end (drained; before a role changes)
 int check_err(rmq_engine* e);
 int event_wait(hipEvent_t ev);  // spin on queries (20 ms), then block
 int stream_wait(hipStream_t s);  // the same for everything issued on a stream
 hipEvent_t pool_event(rmq_engine* e);
+// append.cpp
+int flush(rmq_engine* e);
+int drain(rmq_engine* e);
+int quiesce(rmq_engine* e);
+int settle(rmq_engine* e);  // drain, or with a transport (where a flush is collective) quiesce
 int late_retention(rmq_engine* e);  // the last applied group's retention, where its own launch stopped early
+void dump_stamps(rmq_engine* e);    // RMQ_STAMPS: the stamped launch's phase stamps, at destruction
+void staging_free(rmq_engine* e);
+// offsets.cpp
+int poll_offsets(rmq_engine* e, uint64_t ticket);  // rmq_poll_commit of a consumer-offset ticket (device set)
+void offsets_free(rmq_engine* e);
 // fetch.cpp
 int fetch_flush(rmq_engine* e);  // launch the asynchronous fetches held back (under mu)
 void fetch_free(rmq_engine* e);
@@ -662,7 +665,7 @@ struct EngineLock {
 // RMQ_AUDIT_WGS of them.
 inline uint32_t audit_wgs(const rmq_engine* e) {
   const uint32_t wgs = std::max<uint32_t>(e->cu_count, 1u) * 8u;
-  return e->audit_wgs ? std::min(wgs, e->audit_wgs) : wgs;
+  return e->knob.audit_wgs ? std::min(wgs, e->knob.audit_wgs) : wgs;
 }
 // audit.cpp
 void audit_free(rmq_engine* e);

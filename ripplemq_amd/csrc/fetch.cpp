@@ -298,9 +298,9 @@ void fetch_stage_rows(rmq_engine* e, rmq_engine::FetchSlot& f, const FetchCall& 
     p.d_rq = f.h_req;
     p.d_rs = f.h_res;
   }
-  p.dma = !p.rows_dev && (e->fetch_dma >= 2 || (e->fetch_dma == 1 && !c.sync));
+  p.dma = !p.rows_dev && (e->knob.fetch_dma >= 2 || (e->knob.fetch_dma == 1 && !c.sync));
   p.h_rs = p.rows_pinned ? static_cast<void*>(c.res) : static_cast<void*>(f.h_res);
-  p.dma_in = p.dma && e->fetch_dma_in;
+  p.dma_in = p.dma && e->knob.fetch_dma_in;
 }
 
 // Step 5b, a word per request (the byte budgets, the explicit offsets). Host rows: copied now into
@@ -515,7 +515,7 @@ int fetch_launch(rmq_engine* e, rmq_engine::FetchSlot& f, const FetchCall& c, co
   // only the single-ticket resolve reads them; an array whose entries are all RMQ_OFFSET_NONE is read
   // by nothing and launches the plain resolve, but FORMAT.md §7 says so of every call with
   // offsets != NULL.
-  const bool hold = !c.sync && p.plain_pair() && !c.offsets && !p.dma && !e->profile && e->fetch_coalesce > 1;
+  const bool hold = !c.sync && p.plain_pair() && !c.offsets && !p.dma && !e->profile && e->knob.fetch_coalesce > 1;
   int rc = hold ? RMQ_OK : fetch_flush(e);
   if (rc) return rc;
   if (p.dma_in) HIP_TRY(hipStreamWaitEvent(e->main_s, f.ev_in, 0));
@@ -527,7 +527,7 @@ int fetch_launch(rmq_engine* e, rmq_engine::FetchSlot& f, const FetchCall& c, co
     f.args = a;
     f.pending = true;
     e->fpend.push_back(e->fslot_next);
-    return e->fpend.size() >= std::min<uint32_t>(kFetchBatch, e->fetch_coalesce) ? fetch_flush(e) : RMQ_OK;
+    return e->fpend.size() >= std::min<uint32_t>(kFetchBatch, e->knob.fetch_coalesce) ? fetch_flush(e) : RMQ_OK;
   }
   rc = fetch_kernels(e, f, c, p, a);
   if (rc) return rc;

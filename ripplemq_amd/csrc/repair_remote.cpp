@@ -126,7 +126,7 @@ int repair_remote_rounds(rmq_engine* e, const RepairArgs* a, uint32_t wgs, uint6
       q.lists = B.lists;
       q.list_cap = list_cap;
       q.ctr = B.words + kRemoteWCtr;
-      q.peer_bytes = e->repair_peer_bytes;
+      q.peer_bytes = e->knob.repair_peer_bytes;
       q.round = j;
       q.world = W;
       q.ncand = ncand;

@@ -196,7 +196,7 @@ int post_round(rmq_engine* e, uint32_t s) {
   a.stamp = x.round + 1ull;  // (rmq_leader_silent's clock: rounds ingested)
   if (a.stamp > r->stamp) r->stamp = a.stamp;
   r->stamp_time[a.stamp % 64] = std::chrono::steady_clock::now();
-  launch_ingest(a, tasks, items, e->verify_wgs, r->xchg_s);
+  launch_ingest(a, tasks, items, e->knob.verify_wgs, r->xchg_s);
   if (a.n_in) r->nitems_par ^= 1u;  // (prepare ran: it cleared the other half)
   HIP_TRY(hipGetLastError());
   // acks: {log end | status, position} of every in entry back to its leader, fixed sizes both ways
@@ -243,7 +243,7 @@ int repl_attach(rmq_engine* e, Transport* t) {
   }
   int rc = dalloc(&r->d_counters, 7);
   if (!rc) rc = dalloc(&r->d_lastg, e->cfg.num_partitions);
-  if (!rc && !e->st.csnap) rc = dalloc(&e->st.csnap, 2ull * e->cfg.num_partitions);
+  if (!rc && !e->st.csnap) rc = owned_dalloc(e, &e->st.csnap, 2ull * e->cfg.num_partitions);
   if (rc) return rc;
   {
     // both slots start at the current commits (the first plan reads the slot of the launch before)
