@@ -487,6 +487,55 @@ int rmq_fetch_table_async(rmq_engine* e, const rmq_fetch_req* reqs, const uint64
                           uint32_t n, uint32_t mem, uint8_t* out, uint64_t out_cap, rmq_fetch_res* res,
                           uint64_t* rec_row, uint64_t* rec_pos, uint64_t rec_cap, uint64_t* ticket);
 
+/* ---- lag (added after ABI 11 without a bump, as the repairs were: one struct and one function,
+   nothing existing moves) ---- */
+typedef struct rmq_lag_res {   /* 64 bytes */
+  uint64_t start_offset; /* where a fetch of this row would start: off; RMQ_EOFFSET: the first retained offset */
+  uint64_t records;      /* records in [start_offset, high_watermark); 0 if off >= high_watermark */
+  uint64_t bytes;        /* their record bytes: end_pos - start_pos */
+  uint64_t evicted;      /* RMQ_EOFFSET: log_start_offset - off, records retention took before they were read; else 0 */
+  uint64_t start_pos;    /* logical position (FORMAT.md §2) of record start_offset; 0 if records == 0 */
+  uint64_t end_pos;      /* logical position of record high_watermark (log_end_pos when hw == log_end_offset); 0 if records == 0 */
+  uint64_t headroom;     /* record bytes the partition can still take before retention evicts record start_offset
+                            (below); RMQ_OFFSET_NONE if records == 0 */
+  int32_t status;        /* RMQ_OK, RMQ_EOFFSET, RMQ_ENOTLEADER, RMQ_ENOPART, RMQ_EINVAL */
+  uint32_t reserved;     /* 0 */
+} rmq_lag_res;
+/* How far behind a reader is, and how long it has (FORMAT.md §7 "Lag"; a Kafka consumer group's lag,
+   in records and bytes, and the distance to retention). The rows are rmq_fetch_req rows, so a caller
+   builds its rows once, asks for their lag and then fetches them. Row r, every word of its partition
+   read in one pass of one kernel: the checks of a fetch in its order (pidx >= P: RMQ_ENOPART; a
+   partition not led, without RMQ_FETCH_REPLICA: RMQ_ENOTLEADER; consumer >= max_consumers: RMQ_EINVAL;
+   such a row is all 0 but headroom = RMQ_OFFSET_NONE). off is offsets[r] if offsets != NULL and the
+   word is not RMQ_OFFSET_NONE, else the consumer's committed offset (the replica cursor with
+   RMQ_FETCH_REPLICA): what rmq_fetch_at takes as off. end = high_watermark (with RMQ_FETCH_REPLICA
+   this replica's own). off >= end: RMQ_OK, start_offset = off, every count and position 0, headroom =
+   RMQ_OFFSET_NONE. Otherwise off < log_start_offset gives RMQ_EOFFSET with start_offset =
+   log_start_offset and evicted = log_start_offset - off, else RMQ_OK with start_offset = off;
+   records = end - start_offset (a high watermark at or below the log start: 0, with bytes, both
+   positions 0 and headroom RMQ_OFFSET_NONE; status, start_offset and evicted stay); start_pos and
+   end_pos by FORMAT.md §5's lookup; bytes = end_pos - start_pos, all 64-bit. headroom =
+   max(floor(start_pos / index_interval) * index_interval, log_start_pos) + ring bytes - log_end_pos
+   (0 for a state with more than the ring's bytes retained): record start_offset survives every
+   sequence of appends to the partition whose record bytes total at most headroom, and from the
+   present state one batch that carries 16 bytes more evicts it (where FORMAT.md §3 allows the batch).
+   max_records is not read; RMQ_FETCH_REPLICA is honoured; RMQ_FETCH_COMMIT and RMQ_FETCH_VERIFY are
+   accepted and do nothing (the call never commits, copies or verifies, and any number of rows may
+   name one consumer); any other flag bit of a host row fails the call (RMQ_EINVAL) before anything
+   runs; of a device row only the replica bit is looked at.
+   mem is RMQ_MEM_HOST (reqs, offsets, res ordinary host arrays, staged through page-locked scratch
+   of the call's own: no fetch slot is taken and no fetch ticket retired) or RMQ_MEM_DEVICE (reqs and
+   res 16-byte aligned, offsets 8-byte aligned, RMQ_EINVAL otherwise; used in place); anything else,
+   any RMQ_FETCH_* bit included, is RMQ_EINVAL, and so are a null engine and n != 0 with null reqs or
+   res; n == 0 returns RMQ_OK and touches nothing; the argument checks come before any device call.
+   Synchronous, from any thread. Ordered as rmq_fetch is: its kernel goes to the pipeline stream after
+   every launch and call issued before it and before those issued after it, and the call waits for
+   that kernel alone; it never flushes the forming group, never drains, is not collective with a
+   transport, and writes nothing of the engine (no consumer row, cursor, position-cache entry or
+   round). Returns RMQ_OK with per-row statuses, or RMQ_EINVAL, RMQ_ENOMEM, RMQ_EDEVICE. */
+int rmq_lag(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, uint32_t n, uint32_t mem,
+            rmq_lag_res* res);
+
 /* ---- replication transport (FORMAT.md §9) ---- */
 /* 128-byte communicator id: one rank creates it, the application hands it to every rank. */
 int rmq_rccl_unique_id(uint8_t* out /* 128 bytes */);
@@ -774,7 +823,8 @@ int rmq_host_unregister(rmq_engine* e, void* p);
    launches = calls. 8: rmq_reindex, an event before its first plan to one after its last kernel,
    launches = calls. 9: the record-table kernels of rmq_fetch_table, an event before the first to one
    after the last, launches = calls (such a fetch runs once, without dispatch spans, as a budgeted
-   one; its table kernels lie inside its region 4 too). */
+   one; its table kernels lie inside its region 4 too). 10: rmq_lag, an event before its kernel to one
+   after it, launches = calls. */
 int rmq_profile_enable(rmq_engine* e, int enable);
 int rmq_profile_query(rmq_engine* e, int kernel, uint64_t* launches, double* total_ms);
 /* Device name / CU count for reports. */

@@ -152,6 +152,13 @@ class RmqRestoreRes(C.Structure):
     _fields_ = [("records", u64), ("bytes", u64), ("bad_offset", u64), ("bad_kind", u32), ("status", i32)]
 
 
+class RmqLagRes(C.Structure):
+    _fields_ = [
+        ("start_offset", u64), ("records", u64), ("bytes", u64), ("evicted", u64), ("start_pos", u64),
+        ("end_pos", u64), ("headroom", u64), ("status", i32), ("reserved", u32),
+    ]
+
+
 class RmqAppendStats(C.Structure):
     _fields_ = [
         ("records", u32), ("appended", u32), ("rejected_not_leader", u32),
@@ -193,6 +200,7 @@ _SIGS = {
     "rmq_fetch_at_async": (C.c_int, [vp, vp, vp, vp, u32, u32, vp, u64, vp, C.POINTER(u64)]),
     "rmq_fetch_table": (C.c_int, [vp, vp, vp, vp, u32, u32, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]),
     "rmq_fetch_table_async": (C.c_int, [vp, vp, vp, vp, u32, u32, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]),
+    "rmq_lag": (C.c_int, [vp, vp, vp, u32, u32, vp]),
     "rmq_get_partition_state": (C.c_int, [vp, u32, C.POINTER(RmqPartitionState)]),
     "rmq_get_partition_states": (C.c_int, [vp, u32, u32, vp]),
     "rmq_read_segment": (C.c_int, [vp, u32, u32, u64, u64, vp]),

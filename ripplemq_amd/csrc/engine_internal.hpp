@@ -1,7 +1,7 @@
 // engine_internal.hpp — the engine object shared by the host-side translation units
 // (engine.cpp: creation, destruction, memory, profiling and transport attach; append.cpp: the append
 // pipeline and its tickets; offsets.cpp: consumer-offset commits and acks; control.cpp: roles,
-// placement, votes, ring moves; inspect.cpp: read-backs and fault injection; fetch.cpp: the fetch calls;
+// placement, votes, ring moves; inspect.cpp: read-backs and fault injection; fetch.cpp: the fetch calls; lag.cpp: rmq_lag;
 // audit.cpp: scrub, repair, reindex, remote repair, restore; replication.cpp: replica-log rounds;
 // repair_remote.cpp: the rounds of rmq_repair_remote). launch_plan.hpp holds the knobs and the role
 // grid of a launch, free of the device runtime.
@@ -416,6 +416,17 @@ struct rmq_engine {
   std::deque<std::array<uint64_t, 3>> fetch_done;  // {ticket, rc, bytes used} completed, not yet polled
   std::vector<uint32_t> fpend;  // slots of asynchronous fetches whose kernels wait for fetch_flush (under mu)
 
+  // ---- rmq_lag (lag.cpp): calls serialised by lag_mu (taken before mu); the page-locked staging of
+  // host rows, grown on demand, and the event behind the call's kernel
+  std::mutex lag_mu;
+  struct Lag {
+    rmq_fetch_req* h_req = nullptr;  // [cap]
+    uint64_t* h_at = nullptr;        // [cap] explicit offsets
+    rmq_lag_res* h_res = nullptr;    // [cap]
+    uint32_t cap = 0;
+    hipEvent_t ev = nullptr;
+  } lag;
+
   // ---- consumer commits: staging slots (pinned items -> device by one copy on the pipeline
   // stream), so a commit is ordered with the append stream without waiting for it
   struct CommitSlot {
@@ -443,7 +454,7 @@ struct rmq_engine {
 
   // ---- profile: pipeline launches are timed as one region (event before the first launch after
   // enable, event at the next drain) so no per-launch events sit between kernels; fetch kernels
-  // keep per-launch event pairs (prof[3], prof[4]), and so do every rmq_scrub (prof[2]), every rmq_repair (prof[5]), every rmq_repair_remote (prof[6]), every rmq_restore (prof[7]), every rmq_reindex (prof[8]) and every fetch's record-table kernels (prof[9])
+  // keep per-launch event pairs (prof[3], prof[4]), and so do every rmq_scrub (prof[2]), every rmq_repair (prof[5]), every rmq_repair_remote (prof[6]), every rmq_restore (prof[7]), every rmq_reindex (prof[8]), every fetch's record-table kernels (prof[9]) and every rmq_lag (prof[10])
   uint32_t profile = 0;
   uint32_t fetch_replay = 1;     // rmq_profile_enable(k >= 2): each fetch's kernels run k times
   uint64_t prof_fetch_runs = 0;
@@ -452,7 +463,7 @@ struct rmq_engine {
     hipEvent_t t0 = nullptr, t1 = nullptr;
     bool started = false, ended = false;
   } region;
-  std::vector<EvPair> prof[10];
+  std::vector<EvPair> prof[11];
 
   // ---- per-subsystem scratch, grown on demand and freed by its subsystem
   // ack scratch (offsets.cpp)
@@ -652,6 +663,8 @@ void offsets_free(rmq_engine* e);
 // fetch.cpp
 int fetch_flush(rmq_engine* e);  // launch the asynchronous fetches held back (under mu)
 void fetch_free(rmq_engine* e);
+// lag.cpp
+void lag_free(rmq_engine* e);  // the staging of host rows (its event goes with the engine)
 // The engine lock of every call: held-back asynchronous fetches go to the pipeline stream first, so
 // whatever the call issues is ordered after them (their contract); a launch error stays sticky on the
 // stream and surfaces at the next check.

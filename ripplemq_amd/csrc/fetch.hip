@@ -29,6 +29,9 @@
 //          requests): out_cap bounds the whole call: a prefix scan over the requests' bytes finds
 //          the request that crosses the end of the output, which is cut by the trim's own search
 //          and walk; the served requests after it are put off (RMQ_PENDING).
+//  lag     (rmq_lag, a call of its own; the resolve's shape and its search): per row the records and
+//          bytes between the reader and the high watermark and the partition's retention headroom;
+//          writes nothing of the engine.
 //
 // The kernels (resolve, gather; the chunk sums a slot's previous gather cleared) run on the
 // pipeline stream itself, after the last pipeline launch the host had issued and before the next
@@ -42,6 +45,7 @@
 #include "device_common.hpp"
 #include "fetch_table_walk.hpp"
 #include "kernels.hpp"
+#include "lag_row.hpp"
 
 namespace rmq {
 
@@ -990,6 +994,93 @@ void launch_fetch_table(const FetchTableArgs& a, uint32_t max_wgs, hipStream_t s
   hipLaunchKernelGGL(fetch_table_walk_kernel, dim3(wgs), dim3(kTW), 0, s, a);
 }
 
+// ---------------------------------------------------------------------------------------------
+// rmq_lag (FORMAT.md §7 "Lag"): how far behind a reader is, in records and bytes, and how many bytes
+// its partition can still take before retention evicts what it has not read
+// ---------------------------------------------------------------------------------------------
+static_assert(kLagRows == kRW * kRPW, "the lag kernel has the resolve's shape");
+
+// The resolve's shape: a half-wave per row, two per wave; the workgroup's rows (and their explicit
+// offsets) read once by consecutive 16-byte (8-byte) loads through LDS; every word of the partition
+// in one round; the positions of the slice's two ends, record start_offset and record
+// high_watermark, found together by a quarter-wave each with the resolve's own search
+// (record_posq, no position cache: nothing here is keyed by a consumer's last slice). The row
+// arithmetic is lag_row.hpp's, all of it 64-bit. Each row leaves as one 64-byte record, four
+// 16-byte stores of consecutive lanes. Nothing of the engine is written.
+__global__ __launch_bounds__(64 * kRW) void lag_kernel(LagArgs a) {
+  const DevState& st = a.st;
+  const u32 lane = lane_id(), w = threadIdx.x >> 6;
+  const u32 r = (blockIdx.x * kRW + w) * kRPW + (lane >> 5);
+  const bool live = r < a.n;  // (no early return: the workgroup meets at the barrier below)
+  __shared__ uint4 s_rq[kLagRows];
+  __shared__ u64 s_at[kLagRows];
+  {
+    const u32 r0 = blockIdx.x * kLagRows + threadIdx.x;
+    if (threadIdx.x < kLagRows && r0 < a.n) {
+      const uint4 x = *reinterpret_cast<const uint4*>(a.req + 4ull * r0);
+      s_at[threadIdx.x] = a.at ? a.at[r0] : ~0ull;
+      s_rq[threadIdx.x] = x;
+    }
+  }
+  __syncthreads();
+  const uint4 rq = live ? s_rq[w * kRPW + (lane >> 5)] : make_uint4(0, 0, 0, 0);
+  const u64 at = live ? s_at[w * kRPW + (lane >> 5)] : ~0ull;
+  const u32 p = rq.x, c = rq.y;
+  const bool okp = live && p < st.P;
+  const u32 pp = okp ? p : 0u, cc = c < st.C ? c : 0u;
+  const u32 lead = okp ? st.is_leader[pp] : 0u;
+  const bool rep = (rq.w & kFetchReplica) != 0;  // (max_records and every other flag bit: not read)
+  const u64 tab = okp ? (rep ? st.rcur[pp] : st.cons[(u64)pp * st.C + cc]) : 0ull;
+  const u64 hw = okp ? st.hw[pp] : 0ull;
+  PartView v;
+  v.leo = okp ? st.leo[pp] : 0ull;
+  v.used = okp ? st.used[pp] : 0ull;
+  v.start_off = okp ? st.start_off[pp] : 0ull;
+  v.start_pos = okp ? st.start_pos[pp] : 0ull;
+  const u32 lm = okp ? st.local_mask[pp] : 0u;
+  const u64 desc = okp ? st.ring[pp] : 0ull;
+  const u64 off = okp && at != ~0ull ? at : tab;
+  v.rg = ring_ref(desc, st.interval_log2, st.icap_mul);
+  v.ring = st.logs;
+  int status = kOk;
+  LagPlan pl{0, 0, 0, kOk};
+  bool ok = false;  // the row passed the checks
+  if (!live) {
+  } else if (p >= st.P) {
+    status = kNoPart;
+  } else if (!lead && !rep) {
+    status = kNotLeader;
+  } else if (c >= st.C) {
+    status = kInval;
+  } else {
+    pl = lag_plan(off, hw, v.start_off);
+    ok = true;
+  }
+  const bool need = ok && pl.records > 0;  // both ends are searched
+  if (need) {
+    const u32 r0 = lm ? (u32)__ffs(lm) - 1u : 0u;
+    v.ring = st.logs + (u64)r0 * st.rstride + v.rg.base;
+  }
+  // quarter 0 of the half: record start_offset, quarter 1: record high_watermark
+  const u32 hb = lane & 32u;
+  const u64 pq = record_posq(st, v, (lane & 16u) ? hw : pl.start_offset, need, false, 0ull, 0ull);
+  const u64 pos0 = __shfl(pq, (int)hb, 64), pend = __shfl(pq, (int)(hb + 16u), 64);
+  LagRow row{0, 0, 0, 0, 0, 0, kLagNone, status};
+  if (ok) row = lag_row(pl, pos0, pend, v.start_pos, v.used, v.rg.seg, st.interval_log2);
+  static_assert(sizeof(LagRow) >= 60, "seven words and the status");
+  const u32 j = lane & 31u;
+  if (live && j < 4u) {
+    const u64 x0 = j == 0u ? row.start_offset : j == 1u ? row.bytes : j == 2u ? row.start_pos : row.headroom;
+    const u64 x1 = j == 0u ? row.records : j == 1u ? row.evicted : j == 2u ? row.end_pos : (u64)(uint32_t)row.status;
+    *reinterpret_cast<ulonglong2*>(a.res + 8ull * r + 2ull * j) = make_ulonglong2(x0, x1);
+  }
+}
+
+void launch_lag(const LagArgs& a, hipStream_t s) {
+  if (!a.n) return;
+  hipLaunchKernelGGL(lag_kernel, dim3((a.n + kLagRows - 1) / kLagRows), dim3(64 * kRW), 0, s, a);
+}
+
 // ev[4]: start / end events of the two kernels, recorded by the dispatches themselves
 // (profiling: kernel time without the host's launch gaps), or null
 // Load the fetch kernels' code at engine creation (a process's first launch of a kernel otherwise
@@ -1006,6 +1097,7 @@ void preload_fetch_kernels() {
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_table_sum_kernel));
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_table_rows_kernel));
   (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&fetch_table_walk_kernel));
+  (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&lag_kernel));
 }
 
 static void launch_batch(const FetchBatch& b, hipStream_t s, const hipEvent_t* e) {

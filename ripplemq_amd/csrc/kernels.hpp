@@ -399,6 +399,17 @@ struct FetchTableArgs {
   uint32_t n;
   uint32_t pad;
 };
+// rmq_lag (FORMAT.md §7 "Lag"): one kernel of the resolve's shape, its own arguments. It reads the
+// rows and the partition state and writes the result rows; nothing of the engine is written.
+struct LagArgs {
+  DevState st;
+  const uint32_t* req;       // [n][4] rmq_fetch_req rows: page-locked host or device memory, 16-byte aligned
+  const uint64_t* at;        // [n] explicit offsets (RMQ_OFFSET_NONE: the table's), or null: none
+  uint64_t* res;             // [n][8] rmq_lag_res rows: page-locked host or device memory, 16-byte aligned
+  uint32_t n;
+  uint32_t pad;
+};
+constexpr uint32_t kLagRows = 16;  // rows per workgroup of the lag kernel (the resolve's: 8 waves, two rows each)
 
 
 struct ConsumerCommitArgs {  // one item per (partition, consumer): the host resolved last-writer-wins
@@ -629,6 +640,7 @@ void launch_fetch_budget(const FetchArgs& a, const FetchTrimArgs& t, hipStream_t
 void launch_fetch_fill(const FetchArgs& a, const FetchFillArgs& f, hipStream_t s);
 void launch_fetch_verify(const FetchVerifyArgs& a, uint32_t max_wgs, hipStream_t s);  // after the ticket's gather
 void launch_fetch_table(const FetchTableArgs& a, uint32_t max_wgs, hipStream_t s);  // after the gather and the verify
+void launch_lag(const LagArgs& a, hipStream_t s);  // rmq_lag's one kernel
 void preload_fetch_kernels();
 
 void launch_consumer_commit(const ConsumerCommitArgs& a, hipStream_t s);

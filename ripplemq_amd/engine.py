@@ -91,6 +91,10 @@ FETCH_RES_DTYPE = np.dtype([
     ("start_offset", "<u8"), ("out_pos", "<u8"), ("count", "<u4"), ("bytes", "<u4"),
     ("status", "<i4"), ("reserved", "<u4"),
 ])
+LAG_RES_DTYPE = np.dtype([
+    ("start_offset", "<u8"), ("records", "<u8"), ("bytes", "<u8"), ("evicted", "<u8"), ("start_pos", "<u8"),
+    ("end_pos", "<u8"), ("headroom", "<u8"), ("status", "<i4"), ("reserved", "<u4"),
+])
 SCRUB_RES_DTYPE = np.dtype([
     ("records_ok", "<u8"), ("bytes_ok", "<u8"), ("bad_offset", "<u8"), ("bad_replica", "<u4"),
     ("bad_kind", "<u4"), ("replicas", "<u4"), ("status", "<i4"),
@@ -619,6 +623,28 @@ class Engine:
         if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
             raise EngineError(rc, "rmq_fetch_poll")
         return (rc, tk.res, int(used.value)) + (tuple(tk.table) if tk.table else ())
+
+    def lag(self, pidx, consumer, offsets=None, replica: bool = False, flags: int = 0) -> np.ndarray:
+        """rmq_lag with host rows (FORMAT.md §7 "Lag"): per (pidx[r], consumer[r]) the records and
+        bytes between the reader and the high watermark and the partition's retention headroom, as
+        LAG_RES_DTYPE rows. offsets: explicit offsets as for fetch (an array, or one value for all;
+        None or RMQ_OFFSET_NONE entries: the committed offset, or the replica cursor); replica:
+        RMQ_FETCH_REPLICA on every row; flags: further flag bits for every row (RMQ_FETCH_COMMIT
+        and RMQ_FETCH_VERIFY do nothing, any other fails the call). Writes nothing of the engine."""
+        n = len(pidx)
+        req = np.zeros((n, 4), np.uint32)
+        req[:, 0], req[:, 1] = pidx, consumer
+        req[:, 3] = (A.RMQ_FETCH_REPLICA if replica else 0) | flags
+        at = _offsets(offsets, n)
+        res = np.zeros(n, LAG_RES_DTYPE)
+        _check(self.lib.rmq_lag(self.h, _ptr(req), _ptr(at), n, A.RMQ_MEM_HOST, _ptr(res)), "rmq_lag")
+        return res
+
+    def lag_device(self, d_req: int, d_offsets: int | None, n: int, d_res: int) -> None:
+        """rmq_lag with rows in device memory, used in place: d_req ([n, 4] uint32) and d_res
+        (LAG_RES_DTYPE[n]) 16-byte aligned, d_offsets (uint64[n], 8-byte aligned) or None / 0."""
+        _check(self.lib.rmq_lag(self.h, C.c_void_p(d_req), C.c_void_p(d_offsets or None), n, A.RMQ_MEM_DEVICE,
+                                C.c_void_p(d_res)), "rmq_lag")
 
     def set_segments(self, pidx, segment_bytes) -> None:
         """Ring sizes of partitions pidx[i] (rmq_set_segments: retention at a smaller size first, the

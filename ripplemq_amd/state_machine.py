@@ -381,6 +381,19 @@ class PartitionBroker:
             return 0  # consumerOffsets.getOrDefault(consumerId, 0L)
         return int(self.engine.consumer_offsets(p)[c])
 
+    def consumer_lag(self, group_ids, consumer_ids) -> np.ndarray:
+        """How far consumer consumer_ids[r] is behind on partition group_ids[r], and how long it
+        has: the rmq_lag rows (LAG_RES_DTYPE: records, bytes, evicted, headroom, ...; FORMAT.md §7
+        "Lag") of one call. An unknown group is a row RMQ_ENOPART; a consumer never seen stands at
+        offset 0, as getConsumerOffset has it."""
+        P = self.engine.cfg.num_partitions
+        pidx = np.array([P if self.dir.pidx(g) is None else self.dir.pidx(g) for g in group_ids], np.uint32)
+        known = [self.dir.consumers.get(c) for c in consumer_ids]
+        cons = np.array([0 if c is None else c for c in known], np.uint32)
+        # (a consumer without a row has committed nothing: its offset is 0, whatever row 0 holds)
+        offs = [0 if c is None else None for c in known]
+        return self.engine.lag(pidx, cons, offsets=offs)
+
     # ---- PartitionStateMachine.onLeaderStart -> engine leadership (term bookkeeping)
     def onLeaderStart(self, group_id: str, term: int) -> None:
         self.engine.become_leader(self.dir.pidx(group_id), int(term))

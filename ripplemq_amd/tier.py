@@ -410,6 +410,19 @@ class DurableLog:
         except Exception:  # noqa: BLE001 - interpreter shutdown
             pass
 
+    def backlog(self) -> dict[int, tuple[int, int]]:
+        """{partition: (records, bytes)} between the replica cursor and the replica's commit: what
+        the next spill would write, from one rmq_lag call with RMQ_FETCH_REPLICA (FORMAT.md §7
+        "Lag"); nothing moves. A partition whose cursor fell below the ring counts what is left."""
+        pidx = np.fromiter(self.parts, np.uint32, len(self.parts))
+        if not len(pidx):
+            return {}
+        rows = self.engine.lag(pidx, np.full(len(pidx), self.cursor, np.uint32), replica=True)
+        bad = np.flatnonzero((rows["status"] != A.RMQ_OK) & (rows["status"] != A.RMQ_EOFFSET))
+        if bad.size:
+            raise RuntimeError(f"rmq_lag: partition {int(pidx[bad[0]])}: {A.STATUS_NAMES.get(int(rows['status'][bad[0]]))}")
+        return {int(p): (int(r), int(b)) for p, r, b in zip(pidx, rows["records"], rows["bytes"])}
+
     def spill(self) -> int:
         """Make every committed record durable; returns the number of records written. The host
         time of its phases adds up in self.phase_s (fetch, files, commit, state)."""
