@@ -536,6 +536,77 @@ typedef struct rmq_lag_res {   /* 64 bytes */
 int rmq_lag(rmq_engine* e, const rmq_fetch_req* reqs, const uint64_t* offsets, uint32_t n, uint32_t mem,
             rmq_lag_res* res);
 
+/* ---- record columns (added after ABI 11 without a bump, as rmq_lag was: two structs and one
+   function, nothing existing moves) ---- */
+typedef struct rmq_unpack_args {
+  /* input: the answer of a COMPLETED rmq_fetch_table call with a device output */
+  const uint8_t* buf;        /* the fetch's `out`, device memory, 16-byte aligned */
+  uint64_t buf_bytes;        /* readable bytes at buf (its out_cap or bytes_used) */
+  const rmq_fetch_res* rows; /* [n] its result rows: host memory, or device with RMQ_FETCH_DEVICE_ROWS in mem */
+  const uint64_t* rec_row;   /* [n + 1] device, 8-byte aligned */
+  const uint64_t* rec_pos;   /* [rec_words] device, 8-byte aligned */
+  uint64_t rec_words;
+  const uint32_t* row_tag;   /* [n] device, nullable: tag[j] of row r's records = row_tag[r], else r */
+  /* output, all device memory */
+  uint64_t* rec_first;       /* [n + 1] required: index of row r's first record in the columns; [n] = R */
+  uint64_t* offset;          /* [rec_cap] nullable: header offset of record j */
+  uint32_t* len;             /* [rec_cap] payload length of record j */
+  uint64_t* payload_off;     /* [rec_cap] where record j's payload starts (below) */
+  uint32_t* tag;             /* [rec_cap] nullable */
+  uint64_t rec_cap;
+  uint8_t* payload;          /* nullable: NULL = view mode */
+  uint64_t payload_cap;
+  uint32_t n, stride, mem, flags; /* flags 0 */
+} rmq_unpack_args;
+typedef struct rmq_unpack_res {  /* 48 bytes */
+  uint64_t records;        /* R */
+  uint64_t payload_bytes;  /* bytes the payload area needs: view 0, packed sum(len), strided R * stride */
+  uint64_t mismatched;     /* records whose length word disagrees with their table extent */
+  uint64_t truncated;      /* strided: records with len > stride */
+  uint64_t bad_row;        /* lowest row that fails the structure checks; RMQ_OFFSET_NONE if none */
+  int32_t status; uint32_t reserved;
+} rmq_unpack_res;
+/* The answer of a table fetch as columns (FORMAT.md §7 "Record columns"): what a device consumer
+   computes on and what rmq_append takes, made on the device. Row r owns records iff its status is
+   RMQ_OK and count_r > 0 (rmq_fetch_table's rule); record k of it, k in [0, count_r), is the image
+   buf[out_pos_r + rec_pos[rec_row[r] + k], out_pos_r + rec_pos[rec_row[r] + k + 1]). rec_first[r] =
+   the sum of count over the owning rows before r, R = rec_first[n]. Record j = rec_first[r] + k gets
+   offset[j] = the header's offset word, tag[j] = row_tag[r] (r without row_tag), len[j] =
+   min(header len, extent - 16); a record with 16 + align16(header len) != extent counts in
+   `mismatched` (an unverified fetch over a damaged length word: the table's own trust level; fetch
+   with RMQ_FETCH_VERIFY for integrity). Three modes. View (payload == NULL, which needs stride == 0
+   and payload_cap == 0): payload_off[j] = out_pos_r + rec_pos[...] + 16, a byte offset into buf; no
+   byte is copied and {n = R, pidx = tag, len, payload_off, payload = buf, payload_bytes = buf_bytes}
+   is an rmq_batch of RMQ_MEM_DEVICE as it stands. Packed (payload != NULL, stride == 0):
+   payload_off[j] = len[0] + ... + len[j - 1], the payloads back to back; payload_bytes = sum(len).
+   Strided (stride > 0): payload_off[j] = j * stride; the first min(len[j], stride) payload bytes are
+   copied and the rest of the slot is zero, len[j] stays the full length, records with len > stride
+   count in `truncated`; payload_bytes = R * stride.
+   Every table word, length word and position is checked on the device before it is an address, as
+   rmq_restore checks its table. rec_row is non-decreasing with rec_row[n] <= rec_words; every row's
+   word count is the table rule's (count_r + 1, or 0); an owning row has out_pos_r a multiple of 16,
+   out_pos_r + bytes_r <= buf_bytes and count_r <= bytes_r / 16; its words start at 0, are multiples
+   of 16, increase by at least 16 and end at bytes_r. A row that fails any of these fails the call:
+   status and the return value are RMQ_EINVAL, bad_row is the lowest failing row, no column word and
+   no payload byte is written (rec_first may be), no byte outside buf[0, buf_bytes) and no word
+   outside the caller's arrays is read or written. R > rec_cap, or payload_bytes > payload_cap with a
+   payload area, returns RMQ_ENOSPC: rec_first and `out` are written in full (size the arrays from
+   them), no column word and no payload byte is. len == payload_off == NULL with rec_cap == 0 is the
+   size probe (a packed probe passes any non-null payload with payload_cap 0).
+   Checked before any device call, RMQ_EINVAL: a null engine, args or out; mem other than
+   RMQ_MEM_DEVICE or RMQ_MEM_DEVICE | RMQ_FETCH_DEVICE_ROWS; nonzero flags; a misaligned pointer (buf
+   and device rows 16, 64-bit arrays 8, 32-bit arrays 4; payload any); with n != 0 a null rows,
+   rec_row or rec_first, a null rec_pos with rec_words != 0, a null buf with buf_bytes != 0, a null
+   len or payload_off with rec_cap != 0; payload == NULL with a stride or a payload_cap. n == 0
+   returns RMQ_OK with R = 0 and touches nothing but `out`, and rec_first[0] if rec_first is given.
+   Host rows are staged through page-locked scratch of the call's own. Synchronous, from any thread.
+   Ordered as rmq_lag is: its kernels go to the pipeline stream after every launch and call issued
+   before it and before those issued after it, and the call waits for them alone; it never flushes
+   the forming group, never drains, takes no fetch slot, is not collective with a transport and
+   writes nothing of the engine. Returns RMQ_OK, RMQ_ENOSPC, RMQ_EINVAL, RMQ_ENOMEM or RMQ_EDEVICE;
+   `out` is written whenever the argument checks pass. */
+int rmq_unpack(rmq_engine* e, const rmq_unpack_args* a, rmq_unpack_res* out);
+
 /* ---- replication transport (FORMAT.md §9) ---- */
 /* 128-byte communicator id: one rank creates it, the application hands it to every rank. */
 int rmq_rccl_unique_id(uint8_t* out /* 128 bytes */);
@@ -824,7 +895,8 @@ int rmq_host_unregister(rmq_engine* e, void* p);
    launches = calls. 9: the record-table kernels of rmq_fetch_table, an event before the first to one
    after the last, launches = calls (such a fetch runs once, without dispatch spans, as a budgeted
    one; its table kernels lie inside its region 4 too). 10: rmq_lag, an event before its kernel to one
-   after it, launches = calls. */
+   after it, launches = calls. 11: rmq_unpack, an event before its first kernel to one after its
+   last, launches = calls. */
 int rmq_profile_enable(rmq_engine* e, int enable);
 int rmq_profile_query(rmq_engine* e, int kernel, uint64_t* launches, double* total_ms);
 /* Device name / CU count for reports. */

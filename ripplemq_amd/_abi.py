@@ -159,6 +159,22 @@ class RmqLagRes(C.Structure):
     ]
 
 
+class RmqUnpackArgs(C.Structure):
+    _fields_ = [
+        ("buf", vp), ("buf_bytes", u64), ("rows", vp), ("rec_row", vp), ("rec_pos", vp), ("rec_words", u64),
+        ("row_tag", vp), ("rec_first", vp), ("offset", vp), ("len", vp), ("payload_off", vp), ("tag", vp),
+        ("rec_cap", u64), ("payload", vp), ("payload_cap", u64), ("n", u32), ("stride", u32), ("mem", u32),
+        ("flags", u32),
+    ]
+
+
+class RmqUnpackRes(C.Structure):
+    _fields_ = [
+        ("records", u64), ("payload_bytes", u64), ("mismatched", u64), ("truncated", u64), ("bad_row", u64),
+        ("status", i32), ("reserved", u32),
+    ]
+
+
 class RmqAppendStats(C.Structure):
     _fields_ = [
         ("records", u32), ("appended", u32), ("rejected_not_leader", u32),
@@ -201,6 +217,7 @@ _SIGS = {
     "rmq_fetch_table": (C.c_int, [vp, vp, vp, vp, u32, u32, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]),
     "rmq_fetch_table_async": (C.c_int, [vp, vp, vp, vp, u32, u32, vp, u64, vp, vp, vp, u64, C.POINTER(u64)]),
     "rmq_lag": (C.c_int, [vp, vp, vp, u32, u32, vp]),
+    "rmq_unpack": (C.c_int, [vp, vp, vp]),
     "rmq_get_partition_state": (C.c_int, [vp, u32, C.POINTER(RmqPartitionState)]),
     "rmq_get_partition_states": (C.c_int, [vp, u32, u32, vp]),
     "rmq_read_segment": (C.c_int, [vp, u32, u32, u64, u64, vp]),

@@ -172,6 +172,7 @@ void free_engine(rmq_engine* e) {
   fetch_free(e);
   lag_free(e);
   if (e->lag.ev) hipEventDestroy(e->lag.ev);
+  unpack_free(e);
   staging_free(e);
   offsets_free(e);
   if (e->state_stage) hipHostFree(e->state_stage);
@@ -589,7 +590,7 @@ int rmq_profile_enable(rmq_engine* e, int enable) {
 }
 
 int rmq_profile_query(rmq_engine* e, int kernel, uint64_t* launches, double* total_ms) {
-  if (!e || kernel < 0 || kernel > 10) return RMQ_EINVAL;
+  if (!e || kernel < 0 || kernel > 11) return RMQ_EINVAL;
   EngineLock g(e);
   int rc = begin_call(e, settle);
   if (rc) return rc;

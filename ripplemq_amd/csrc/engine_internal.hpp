@@ -1,7 +1,7 @@
 // engine_internal.hpp — the engine object shared by the host-side translation units
 // (engine.cpp: creation, destruction, memory, profiling and transport attach; append.cpp: the append
 // pipeline and its tickets; offsets.cpp: consumer-offset commits and acks; control.cpp: roles,
-// placement, votes, ring moves; inspect.cpp: read-backs and fault injection; fetch.cpp: the fetch calls; lag.cpp: rmq_lag;
+// placement, votes, ring moves; inspect.cpp: read-backs and fault injection; fetch.cpp: the fetch calls; lag.cpp: rmq_lag; unpack.cpp: rmq_unpack;
 // audit.cpp: scrub, repair, reindex, remote repair, restore; replication.cpp: replica-log rounds;
 // repair_remote.cpp: the rounds of rmq_repair_remote). launch_plan.hpp holds the knobs and the role
 // grid of a launch, free of the device runtime.
@@ -427,6 +427,22 @@ struct rmq_engine {
     hipEvent_t ev = nullptr;
   } lag;
 
+  // ---- rmq_unpack (unpack.cpp): calls serialised by unpack_mu (taken before mu); the page-locked
+  // staging of host rows and their device copy, the chunk-sum scratch, the control words on both
+  // sides, all grown on demand, and the event behind the call's last copy
+  std::mutex unpack_mu;
+  struct Unpack {
+    rmq_fetch_res* h_rows = nullptr;  // [row_cap] page-locked
+    uint64_t* d_rows = nullptr;       // [row_cap][4]
+    uint64_t* d_rsum = nullptr;       // [row_cap / kFetchChunk + 1]
+    uint32_t row_cap = 0;
+    uint64_t* d_lsum = nullptr;       // [lsum_cap]
+    uint64_t lsum_cap = 0;
+    uint64_t* h_ctl = nullptr;        // [kUnpackCtlWords] page-locked
+    uint64_t* d_ctl = nullptr;        // [kUnpackCtlWords]
+    hipEvent_t ev = nullptr;
+  } unpack;
+
   // ---- consumer commits: staging slots (pinned items -> device by one copy on the pipeline
   // stream), so a commit is ordered with the append stream without waiting for it
   struct CommitSlot {
@@ -454,7 +470,7 @@ struct rmq_engine {
 
   // ---- profile: pipeline launches are timed as one region (event before the first launch after
   // enable, event at the next drain) so no per-launch events sit between kernels; fetch kernels
-  // keep per-launch event pairs (prof[3], prof[4]), and so do every rmq_scrub (prof[2]), every rmq_repair (prof[5]), every rmq_repair_remote (prof[6]), every rmq_restore (prof[7]), every rmq_reindex (prof[8]), every fetch's record-table kernels (prof[9]) and every rmq_lag (prof[10])
+  // keep per-launch event pairs (prof[3], prof[4]), and so do every rmq_scrub (prof[2]), every rmq_repair (prof[5]), every rmq_repair_remote (prof[6]), every rmq_restore (prof[7]), every rmq_reindex (prof[8]), every fetch's record-table kernels (prof[9]), every rmq_lag (prof[10]) and every rmq_unpack (prof[11])
   uint32_t profile = 0;
   uint32_t fetch_replay = 1;     // rmq_profile_enable(k >= 2): each fetch's kernels run k times
   uint64_t prof_fetch_runs = 0;
@@ -463,7 +479,7 @@ struct rmq_engine {
     hipEvent_t t0 = nullptr, t1 = nullptr;
     bool started = false, ended = false;
   } region;
-  std::vector<EvPair> prof[11];
+  std::vector<EvPair> prof[12];
 
   // ---- per-subsystem scratch, grown on demand and freed by its subsystem
   // ack scratch (offsets.cpp)
@@ -665,6 +681,8 @@ int fetch_flush(rmq_engine* e);  // launch the asynchronous fetches held back (u
 void fetch_free(rmq_engine* e);
 // lag.cpp
 void lag_free(rmq_engine* e);  // the staging of host rows (its event goes with the engine)
+// unpack.cpp
+void unpack_free(rmq_engine* e);  // rmq_unpack's staging, scratch and event
 // The engine lock of every call: held-back asynchronous fetches go to the pipeline stream first, so
 // whatever the call issues is ordered after them (their contract); a launch error stays sticky on the
 // stream and surfaces at the next check.

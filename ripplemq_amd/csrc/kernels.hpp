@@ -669,6 +669,44 @@ void launch_remote_install(const RemoteInstallArgs& a, hipStream_t s);
 void launch_restore_verify(const RestoreArgs& a, uint64_t records, uint32_t max_wgs, hipStream_t s);
 void launch_restore_install(const RestoreArgs& a, uint64_t records, uint32_t max_wgs, hipStream_t s);  // records, then state
 
+// rmq_unpack (FORMAT.md §7 "Record columns"; unpack.hip): the answer of a table fetch as columns. The
+// caller's arrays as the C struct names them, and the call's scratch.
+enum : uint32_t { kUnpackView = 0, kUnpackPacked = 1, kUnpackStrided = 2 };
+// The control words of one call (device, zeroed before its first kernel, read back after its last).
+enum : uint32_t {
+  kUnpackBad = 0,        // max over failing rows of n - r (0: none), so the lowest failing row wins
+  kUnpackRecords = 1,    // R
+  kUnpackBytes = 2,      // payload_bytes
+  kUnpackMismatch = 3,   // records whose length word disagrees with their extent
+  kUnpackTrunc = 4,      // strided: records with len > stride
+  kUnpackStop = 5,       // a capacity is short: no column word and no payload byte is written
+  kUnpackCtlWords = 8,
+};
+constexpr uint32_t kUnpackChunk = 256;  // records per chunk sum of len (a workgroup's records)
+struct UnpackArgs {
+  const uint8_t* buf;
+  uint64_t buf_bytes;
+  const uint64_t* rows;      // [n][4] rmq_fetch_res rows in device memory, 16-byte aligned
+  const uint64_t* rec_row;   // [n + 1]
+  const uint64_t* rec_pos;   // [rec_words]
+  uint64_t rec_words;
+  const uint32_t* row_tag;   // [n] or null
+  uint64_t* rec_first;       // [n + 1]
+  uint64_t* offset;          // [rec_cap] or null
+  uint32_t* len;             // [rec_cap]
+  uint64_t* payload_off;     // [rec_cap]
+  uint32_t* tag;             // [rec_cap] or null
+  uint64_t rec_cap;
+  uint8_t* payload;
+  uint64_t payload_cap;
+  uint64_t* rsum;            // [chunks of kFetchChunk rows] records of each chunk (scratch)
+  uint64_t* lsum;            // [rec_words / kUnpackChunk + 1] len sums of each record chunk, then their prefix (scratch)
+  uint64_t* ctl;             // [kUnpackCtlWords]
+  uint32_t n, stride, mode, pad;
+};
+// The five launches of a call, in stream order; max_wgs caps the record grids.
+void launch_unpack(const UnpackArgs& a, uint32_t max_wgs, hipStream_t s);
+
 }  // namespace rmq
 
 namespace rmq_x {

@@ -95,6 +95,16 @@ LAG_RES_DTYPE = np.dtype([
     ("start_offset", "<u8"), ("records", "<u8"), ("bytes", "<u8"), ("evicted", "<u8"), ("start_pos", "<u8"),
     ("end_pos", "<u8"), ("headroom", "<u8"), ("status", "<i4"), ("reserved", "<u4"),
 ])
+UNPACK_ARGS_DTYPE = np.dtype([
+    ("buf", "<u8"), ("buf_bytes", "<u8"), ("rows", "<u8"), ("rec_row", "<u8"), ("rec_pos", "<u8"), ("rec_words", "<u8"),
+    ("row_tag", "<u8"), ("rec_first", "<u8"), ("offset", "<u8"), ("len", "<u8"), ("payload_off", "<u8"), ("tag", "<u8"),
+    ("rec_cap", "<u8"), ("payload", "<u8"), ("payload_cap", "<u8"), ("n", "<u4"), ("stride", "<u4"), ("mem", "<u4"),
+    ("flags", "<u4"),
+])
+UNPACK_RES_DTYPE = np.dtype([
+    ("records", "<u8"), ("payload_bytes", "<u8"), ("mismatched", "<u8"), ("truncated", "<u8"), ("bad_row", "<u8"),
+    ("status", "<i4"), ("reserved", "<u4"),
+])
 SCRUB_RES_DTYPE = np.dtype([
     ("records_ok", "<u8"), ("bytes_ok", "<u8"), ("bad_offset", "<u8"), ("bad_replica", "<u4"),
     ("bad_kind", "<u4"), ("replicas", "<u4"), ("status", "<i4"),
@@ -645,6 +655,116 @@ class Engine:
         (LAG_RES_DTYPE[n]) 16-byte aligned, d_offsets (uint64[n], 8-byte aligned) or None / 0."""
         _check(self.lib.rmq_lag(self.h, C.c_void_p(d_req), C.c_void_p(d_offsets or None), n, A.RMQ_MEM_DEVICE,
                                 C.c_void_p(d_res)), "rmq_lag")
+
+    def unpack_device(self, *, buf: int, buf_bytes: int, rows, n: int, rec_row: int, rec_pos: int, rec_words: int,
+                      rec_first: int, len: int = 0, payload_off: int = 0, offset: int = 0, tag: int = 0,  # noqa: A002
+                      row_tag: int = 0, rec_cap: int = 0, payload: int = 0, payload_cap: int = 0, stride: int = 0,
+                      flags: int = 0) -> dict:
+        """rmq_unpack over device addresses (FORMAT.md §7 "Record columns"): the answer of a table
+        fetch into a device buffer as columns. Every array is a device address (0 / None: null) but
+        rows: the fetch's result rows as a FETCH_RES_DTYPE array (host rows), or the address of
+        device rows (RMQ_FETCH_DEVICE_ROWS). payload 0: view mode; stride > 0: strided; else packed.
+        Returns the rmq_unpack_res as a dict (status RMQ_OK or RMQ_ENOSPC); raises on anything else,
+        the error's `res` attribute holding the dict."""
+        mem = A.RMQ_MEM_DEVICE
+        if isinstance(rows, np.ndarray):
+            rows = np.ascontiguousarray(rows)
+            p_rows = _ptr(rows)
+        else:
+            p_rows, mem = rows or None, mem | A.RMQ_FETCH_DEVICE_ROWS
+        a = A.RmqUnpackArgs(buf or None, buf_bytes, p_rows, rec_row or None, rec_pos or None, rec_words,
+                            row_tag or None, rec_first or None, offset or None, len or None, payload_off or None,
+                            tag or None, rec_cap, payload or None, payload_cap, n, stride, mem, flags)
+        out = A.RmqUnpackRes()
+        rc = self.lib.rmq_unpack(self.h, C.byref(a), C.byref(out))
+        d = {f: int(getattr(out, f)) for f, _ in A.RmqUnpackRes._fields_}
+        if rc not in (A.RMQ_OK, A.RMQ_ENOSPC):
+            err = EngineError(rc, "rmq_unpack")
+            err.res = d
+            raise err
+        return d
+
+    def fetch_columns(self, pidx, consumer, max_records, *, mode="packed", row_tag=None, out_cap: int | None = None,
+                      device_rows: bool = False, keep_device: bool = False, **fetch_kw):
+        """A fetch answered as columns (rmq_fetch_table into a device buffer, then rmq_unpack; FORMAT.md
+        §7 "Record columns"): (res, columns, payload). res: the fetch's result rows; columns: a dict
+        of numpy arrays, rec_first (uint64[n + 1]) and per record offset, len, payload_off, tag, plus
+        the rmq_unpack_res words under "unpack"; payload: mode "packed": the payloads back to back
+        (record j is payload[payload_off[j]:payload_off[j] + len[j]]); mode "view": the fetch's own
+        output, payload_off pointing into it; mode an int stride: an [R, stride] array. row_tag:
+        uint32[n], the tag of each row's records (default: the row's index). out_cap: the bytes of
+        the device output (default: sized by a query; required with fill). device_rows: the unpack
+        reads the result rows from device memory. keep_device: the device arrays stay allocated and
+        columns["device"] names them (buf, buf_bytes, offset, len, payload_off, tag, payload, and
+        "held": every address to device_free), e.g. to append the columns as they lie. fetch_kw: commit, verify, max_bytes, offsets, fill,
+        as for fetch_device."""
+        n = len(pidx)
+        stride = 0 if isinstance(mode, str) else int(mode)
+        if (isinstance(mode, str) and mode not in ("packed", "view")) or (not isinstance(mode, str) and stride <= 0):
+            raise ValueError(f"mode: 'packed', 'view' or a positive stride, not {mode!r}")
+        if out_cap is None:
+            if fetch_kw.get("fill"):
+                raise ValueError("fill needs out_cap: a filling fetch has no sizing call")
+            q = {k: fetch_kw[k] for k in ("verify", "max_bytes", "offsets") if k in fetch_kw}
+            out_cap = self.fetch(pidx, consumer, max_records, out_cap=0, **q)[3]
+        out_cap = (int(out_cap) + 15) & ~15
+        words = out_cap // 16 + n
+        held: list[int] = []
+
+        def dev(nbytes, src=None):
+            p = self.device_alloc(max(int(nbytes), 16))
+            held.append(p)
+            if src is not None:
+                self.h2d(p, src)
+            return p
+
+        def back(p, count, dtype):
+            a = np.empty(count, dtype)
+            if count:
+                self.d2h(a, p)
+            return a
+
+        try:
+            d_out, d_row, d_pos, d_first = dev(out_cap), dev(8 * (n + 1)), dev(8 * words), dev(8 * (n + 1))
+            rc, res, used = self.fetch_device(pidx, consumer, max_records, d_out, out_cap,
+                                              table=(d_row, d_pos, words), **fetch_kw)[:3]
+            if rc != A.RMQ_OK:
+                raise EngineError(rc, "rmq_fetch_table (fetch_columns)")
+            rows = dev(res.nbytes, res) if device_rows else res
+            d_tag_in = 0 if row_tag is None else dev(4 * n, np.ascontiguousarray(row_tag, np.uint32))
+            common = dict(buf=d_out, buf_bytes=out_cap, rows=rows, n=n, rec_row=d_row, rec_pos=d_pos, rec_words=words,
+                          rec_first=d_first, row_tag=d_tag_in, stride=stride)
+            # the size probe (a non-null payload selects the mode; nothing is written through it)
+            probe = self.unpack_device(**common, payload=0 if mode == "view" else d_out)
+            R, nb = probe["records"], probe["payload_bytes"]
+            un = probe
+            d_pay = 0
+            if R:
+                d_off, d_len, d_poff, d_tag = dev(8 * R), dev(4 * R), dev(8 * R), dev(4 * R)
+                d_pay = 0 if mode == "view" else dev(nb)
+                un = self.unpack_device(**common, offset=d_off, len=d_len, payload_off=d_poff, tag=d_tag, rec_cap=R,
+                                        payload=d_pay, payload_cap=0 if mode == "view" else nb)
+                if un["status"] != A.RMQ_OK:
+                    raise EngineError(un["status"], "rmq_unpack (fetch_columns)")
+            cols = {"rec_first": back(d_first, n + 1, np.uint64)}
+            for name, p, dt in (("offset", R and d_off, np.uint64), ("len", R and d_len, np.uint32),
+                                ("payload_off", R and d_poff, np.uint64), ("tag", R and d_tag, np.uint32)):
+                cols[name] = back(p, R, dt)
+            cols["unpack"] = un
+            if keep_device:
+                cols["device"] = dict(buf=d_out, buf_bytes=out_cap, offset=R and d_off, len=R and d_len,
+                                      payload_off=R and d_poff, tag=R and d_tag, payload=d_pay, held=list(held))
+                held.clear()
+            if mode == "view":
+                payload = back(d_out, out_cap, np.uint8)
+            else:
+                payload = back(d_pay, nb if R else 0, np.uint8)
+                if stride:
+                    payload = payload.reshape(R, stride)
+            return res, cols, payload
+        finally:
+            for p in held:
+                self.device_free(p)
 
     def set_segments(self, pidx, segment_bytes) -> None:
         """Ring sizes of partitions pidx[i] (rmq_set_segments: retention at a smaller size first, the

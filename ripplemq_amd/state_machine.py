@@ -182,7 +182,7 @@ class PartitionBroker:
     def __init__(self, directory: PartitionDirectory, engine=None, *, replication_factor: int = 1,
                  segment_bytes: int = 1 << 22, index_interval: int = 4096, device: int = 0,
                  messages_as_str: bool = True, durable=None, verify: bool = False,
-                 repair: bool = False, record_table: bool = False):
+                 repair: bool = False, record_table: bool = False, columns: bool = False):
         """verify: reads carry RMQ_FETCH_VERIFY, and a slice with a record that fails its CRC32C or
         framing is answered by a failed MessageBatchReadResponse (no messages, the offset the
         consumer stands at, an error message) instead of being served. Off by default.
@@ -196,7 +196,11 @@ class PartitionBroker:
         evicts, PartitionStateMachine.java:26) instead of failing with RMQ_EOFFSET.
         record_table: reads fetch with a record table (rmq_fetch_table, FORMAT.md §7 "Record table")
         and are split into messages with it (table_records) instead of by chaining length words per
-        record (parse_records); the responses are the same. Off by default."""
+        record (parse_records); the responses are the same. Off by default.
+        columns: reads go through Engine.fetch_columns(mode="packed") (rmq_fetch_table into device
+        memory, then rmq_unpack, FORMAT.md §7 "Record columns"): headers and padding are peeled off
+        on the device and message j is payload[payload_off[j]:payload_off[j] + len[j]]; the
+        responses are the same. Off by default."""
         self.dir = directory
         self.durable = durable
         if engine is None:
@@ -209,6 +213,7 @@ class PartitionBroker:
         self.verify = bool(verify)
         self.repair = bool(repair)
         self.record_table = bool(record_table)
+        self.columns = bool(columns)
         self._sms: dict[str, PartitionStateMachine] = {}
 
     def close(self) -> None:
@@ -309,6 +314,20 @@ class PartitionBroker:
         closure then answers success), RMQ_PENDING, or RMQ_ENOTLEADER (failed by a leader change)."""
         return self.engine.poll_offsets(ticket)
 
+    def _fetch_split(self, p, c, mx, verify: bool):
+        """One fetch of the read path: (res, buf, split); split[k]: request k's records as
+        (offset, crc, payload) by the record table or the columns, or None: parse buf."""
+        kw = {"verify": True} if verify else {}
+        pa, ca, ma = np.asarray(p, np.uint32), np.asarray(c, np.uint32), np.asarray(mx, np.uint32)
+        if self.columns:
+            res, col, pay = self.engine.fetch_columns(pa, ca, ma, mode="packed", **kw)
+            b, first = pay.tobytes(), col["rec_first"].tolist()
+            recs = [(o, None, b[s:s + n]) for o, s, n in zip(col["offset"].tolist(), col["payload_off"].tolist(),
+                                                             col["len"].tolist())]
+            return res, None, [recs[first[k]:first[k + 1]] for k in range(len(p))]
+        _, res, buf, _, *tab = self.engine.fetch(pa, ca, ma, **kw, **({"table": True} if self.record_table else {}))
+        return res, buf, table_records(buf, res, *tab) if tab else None  # every request's records, by the table
+
     # ---- MessageBatchReadRequestProcessor.handleRequest, batched
     def process_batch_read(self, requests: list[MessageBatchReadRequest]) -> list:
         """One MessageBatchReadResponse per request, or the string "Not leader" as the reference
@@ -325,21 +344,14 @@ class PartitionBroker:
             c.append(self.dir.consumer(req.getConsumerId()))
             mx.append(max(int(req.getMaxMessages()), 0))
         if idx:
-            kw = {"table": True} if self.record_table else {}
-            _, res, buf, _, *tab = self.engine.fetch(np.asarray(p, np.uint32), np.asarray(c, np.uint32),
-                                                     np.asarray(mx, np.uint32), **kw,
-                                                     **({"verify": True} if self.verify else {}))
-            split = table_records(buf, res, *tab) if tab else None  # every request's records, by the table
+            res, buf, split = self._fetch_split(p, c, mx, self.verify)
             rows = [(res, buf, k, split) for k in range(len(idx))]
             bad = [k for k in range(len(idx)) if int(res["status"][k]) == A.RMQ_ECORRUPT]
             if bad and self.verify and self.repair:
                 # heal the refused partitions from their clean local replicas, then read those again
                 for pi in sorted({p[k] for k in bad}):
                     self.engine.repair(pi, 1)
-                _, res2, buf2, _, *tab2 = self.engine.fetch(np.asarray([p[k] for k in bad], np.uint32),
-                                                            np.asarray([c[k] for k in bad], np.uint32),
-                                                            np.asarray([mx[k] for k in bad], np.uint32), verify=True, **kw)
-                split2 = table_records(buf2, res2, *tab2) if tab2 else None
+                res2, buf2, split2 = self._fetch_split([p[k] for k in bad], [c[k] for k in bad], [mx[k] for k in bad], True)
                 for j, k in enumerate(bad):
                     rows[k] = (res2, buf2, j, split2)
             spilled = False
