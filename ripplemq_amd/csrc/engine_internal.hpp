@@ -4,7 +4,8 @@
 // placement, votes, ring moves; inspect.cpp: read-backs and fault injection; fetch.cpp: the fetch calls; lag.cpp: rmq_lag; unpack.cpp: rmq_unpack;
 // audit.cpp: scrub, repair, reindex, remote repair, restore; replication.cpp: replica-log rounds;
 // repair_remote.cpp: the rounds of rmq_repair_remote). launch_plan.hpp holds the knobs and the role
-// grid of a launch, free of the device runtime.
+// grid of a launch, repl_plan.hpp the replication lists, buffer bounds and round layout; both are
+// free of the device runtime and checked by stand-alone programs under tools/.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,6 +28,7 @@
 #include "device_common.hpp"
 #include "kernels.hpp"
 #include "launch_plan.hpp"
+#include "repl_plan.hpp"
 #include "transport.hpp"
 
 using namespace rmq;
@@ -38,6 +40,7 @@ constexpr uint32_t kMaxBatchRecords = kMaxTiles * kTileRecs;       // 524288
 // pipeline scratch sets: a group's set lives from its stage 1 (launch k) to the application of its
 // followers' acks (launch k + 5 with a replication transport), so six sets rotate
 constexpr uint32_t kSets = 6;
+static_assert(kPlanMaxWorld == kMaxWorld, "repl_plan.hpp sizes its per-peer arrays for kMaxWorld ranks");
 // rmq_repair_remote's control words (rmq_engine::RemoteRepair::words): the words sent [2 * kMaxWorld]
 // and received [2 * kMaxWorld], RemoteReqArgs::ctr [2 * kMaxWorld + 1], RemoteServeArgs::tot [3 * kMaxWorld]
 constexpr uint32_t kRemoteWSend = 0, kRemoteWRecv = 2 * kMaxWorld, kRemoteWCtr = 4 * kMaxWorld,
@@ -45,6 +48,21 @@ constexpr uint32_t kRemoteWSend = 0, kRemoteWRecv = 2 * kMaxWorld, kRemoteWCtr =
 
 struct EvPair {
   hipEvent_t a = nullptr, b = nullptr;
+};
+
+// Device buffers a subsystem reallocates as a set: each is noted where it is allocated (the address
+// of its pointer) and freed, its pointer nulled, from this record alone (hipFree takes a null).
+struct DevRecord {
+  std::vector<void**> ptrs;
+  template <typename T>
+  void note(T** p) { ptrs.push_back(reinterpret_cast<void**>(p)); }
+  void free_all() {
+    for (void** p : ptrs) {
+      hipFree(*p);
+      *p = nullptr;
+    }
+    ptrs.clear();
+  }
 };
 
 // Device staging of host-memory batches.
@@ -174,10 +192,8 @@ struct Replication {
   Transport* xport = nullptr;
   uint32_t world = 1, rank = 0;
   hipStream_t xchg_s = nullptr;
-  // out list: (led partition, remote slot) grouped by destination, ascending (key, slot);
-  // in list: (followed partition, local slot) grouped by source, same order on both sides
-  std::vector<uint32_t> xo_p, xo_slot, xo_start, xi_p, xi_slot, xi_start;
-  std::vector<uint64_t> keysum;  // [world] of the out lists
+  ReplLists lists;  // the placement's out / in lists (plan_lists), replaced by every placement call
+  DevRecord placed;  // the device buffers sized by the placement (placed_alloc in replication.cpp)
   uint32_t* d_xo_p = nullptr;
   uint32_t* d_xo_start = nullptr;
   uint64_t* d_keysum = nullptr;
@@ -197,6 +213,7 @@ struct Replication {
   uint32_t nitems_par = 0;
   uint64_t* d_counters = nullptr;  // [7]: follower [0..4) (IngestArgs), leader [4..7) (XPlanArgs)
   uint64_t* d_lastg = nullptr;     // [P] record bytes / 16 of the last group applied (PipeArgs::lastg)
+  uint64_t* d_shake = nullptr;     // [8 * kMaxWorld] the placement handshake's words, made at attach
   // leader catch-up state per out entry (FORMAT.md §9 v3)
   uint64_t* d_xnext = nullptr;   // [n_out][2]
   uint64_t* d_xreq = nullptr;    // [n_out][4]
@@ -233,6 +250,26 @@ struct Replication {
   bool flip[kMaxWorld] = {};
   int64_t flip_at[kMaxWorld] = {};
 };
+
+// The arguments of one Transport::exchange: for every peer q the bytes sent from sb[q] and received
+// into rb[q] (this rank's own entries: 0 bytes).
+struct Exchange {
+  void* sb[kMaxWorld];
+  void* rb[kMaxWorld];
+  uint64_t sn[kMaxWorld], rn[kMaxWorld];
+  void peer(uint32_t q, void* s, uint64_t s_bytes, void* r, uint64_t r_bytes) {
+    sb[q] = s, sn[q] = s_bytes, rb[q] = r, rn[q] = r_bytes;
+  }
+  int post(Replication* r) const { return r->xport->exchange(sb, sn, rb, rn, r->xchg_s); }
+};
+// n bytes to and from every peer: peer q's at element q * stride of send and of recv.
+template <typename T>
+Exchange fixed_swap(const Replication* r, T* send, T* recv, uint32_t stride, uint64_t n) {
+  Exchange x;
+  for (uint32_t q = 0; q < r->world; ++q)
+    x.peer(q, send + (size_t)q * stride, q == r->rank ? 0 : n, recv + (size_t)q * stride, q == r->rank ? 0 : n);
+  return x;
+}
 
 }  // namespace rmq
 
@@ -520,6 +557,7 @@ struct rmq_engine {
     uint64_t* words = nullptr;   // [kRemoteWords] exchanged words, counters and totals
     uint64_t* h_words = nullptr; // pinned mirror, then the list headers
     hipEvent_t ev = nullptr;
+    DevRecord dev;               // every device buffer above, noted where repair_remote.cpp makes it
     bool flip[kMaxWorld] = {};   // rmq_fault_corrupt_repair: the next response to q
     int64_t flip_at[kMaxWorld] = {};
   } rr;

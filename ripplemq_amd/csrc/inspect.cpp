@@ -178,8 +178,8 @@ int rmq_replication_stats(rmq_engine* e, rmq_repl_stats* out) {
   if (rc) return rc;
   out->world = r->world;
   out->rank = r->rank;
-  out->out_entries = (uint32_t)r->xo_p.size();
-  out->in_entries = (uint32_t)r->xi_p.size();
+  out->out_entries = (uint32_t)r->lists.xo_p.size();
+  out->in_entries = (uint32_t)r->lists.xi_p.size();
   out->rounds = r->rounds;
   out->bytes_sent = r->bytes_sent;
   out->bytes_received = r->bytes_recv;

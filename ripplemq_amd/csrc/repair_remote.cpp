@@ -19,19 +19,24 @@ namespace rmq {
 
 namespace {
 
-int swap_words(rmq_engine* e, uint32_t W, uint32_t me) {
+// The call's device buffers: dalloc and grow, the buffer noted on the record repair_remote_free frees from.
+template <typename T>
+int rr_alloc(rmq_engine::RemoteRepair& B, T** p, size_t count) {
+  const int rc = dalloc(p, count);
+  if (*p) B.dev.note(p);
+  return rc;
+}
+template <typename T>
+int rr_grow(rmq_engine::RemoteRepair& B, T** p, uint64_t* cap, uint64_t need) {
+  if (!*p) B.dev.note(p);  // (grow keeps the pointer's address)
+  return grow(p, cap, need);
+}
+
+int swap_words(rmq_engine* e, uint32_t W) {
   rmq_engine::RemoteRepair& B = e->rr;
   Replication* r = e->repl;
-  void* sb[kMaxWorld];
-  void* rb[kMaxWorld];
-  uint64_t n16[kMaxWorld];
-  for (uint32_t q = 0; q < W; ++q) {
-    sb[q] = B.words + kRemoteWSend + 2 * q;
-    rb[q] = B.words + kRemoteWRecv + 2 * q;
-    n16[q] = q == me ? 0 : 16;
-  }
   HIP_TRY(hipMemcpyAsync(B.words + kRemoteWSend, B.h_words + kRemoteWSend, 2ull * W * 8, hipMemcpyHostToDevice, r->xchg_s));
-  int rc = r->xport->exchange(sb, n16, rb, n16, r->xchg_s);
+  int rc = fixed_swap(r, B.words + kRemoteWSend, B.words + kRemoteWRecv, 2, 16).post(r);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(B.h_words + kRemoteWRecv, B.words + kRemoteWRecv, 2ull * W * 8, hipMemcpyDeviceToHost, r->xchg_s));
   HIP_TRY(hipStreamSynchronize(r->xchg_s));
@@ -42,9 +47,7 @@ int swap_words(rmq_engine* e, uint32_t W, uint32_t me) {
 
 void repair_remote_free(rmq_engine* e) {
   rmq_engine::RemoteRepair& B = e->rr;
-  void* bufs[] = {B.want, B.fetched, B.cand, B.pkey, B.keys, B.lists, B.rin, B.sv, B.out, B.in, B.csum, B.words};
-  for (void* p : bufs)
-    if (p) hipFree(p);
+  B.dev.free_all();
   if (B.h_words) hipHostFree(B.h_words);
   if (B.ev) hipEventDestroy(B.ev);
   B = rmq_engine::RemoteRepair();
@@ -60,8 +63,8 @@ int repair_remote_rounds(rmq_engine* e, const RepairArgs* a, uint32_t wgs, uint6
   served[0] = served[1] = 0;
   int rc = RMQ_OK;
   if (!B.words) {
-    rc = dalloc(&B.words, kRemoteWords);
-    if (!rc) rc = dalloc(&B.csum, (size_t)kMaxWorld * kRemoteChunks);
+    rc = rr_alloc(B, &B.words, kRemoteWords);
+    if (!rc) rc = rr_alloc(B, &B.csum, (size_t)kMaxWorld * kRemoteChunks);
     if (rc) return rc;
     HIP_TRY(hipHostMalloc((void**)&B.h_words, (kRemoteWords + 2ull * kMaxWorld) * 8, 0));
     HIP_TRY(hipEventCreateWithFlags(&B.ev, hipEventDisableTiming));
@@ -74,8 +77,8 @@ int repair_remote_rounds(rmq_engine* e, const RepairArgs* a, uint32_t wgs, uint6
     for (uint32_t p = 0; p < P; ++p) keys[p] = {e->key[p], p, 0u};
     std::sort(keys.begin(), keys.end(), [](const RemoteKey& x, const RemoteKey& y) { return x.key < y.key; });
     uint64_t cap = B.key_cap;
-    rc = grow(&B.keys, &cap, P);
-    if (!rc) rc = grow(&B.pkey, &B.key_cap, P);
+    rc = rr_grow(B, &B.keys, &cap, P);
+    if (!rc) rc = rr_grow(B, &B.pkey, &B.key_cap, P);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(B.keys, keys.data(), (size_t)P * sizeof(RemoteKey), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(B.pkey, e->key.data(), (size_t)P * 8, hipMemcpyHostToDevice));
@@ -101,17 +104,15 @@ int repair_remote_rounds(rmq_engine* e, const RepairArgs* a, uint32_t wgs, uint6
     }
     max_reqs = (uint32_t)std::min<uint64_t>(kRemoteMaxReqs, std::max<uint64_t>(tasks, 1));
     list_cap = kRemoteHdr + (uint64_t)kRemoteReq * max_reqs;
-    rc = grow(&B.cand, &B.cand_cap, cand.size());
-    if (!rc) rc = grow(&B.want, &B.want_cap, tasks);
-    if (!rc) rc = grow(&B.fetched, &B.fetched_cap, 2ull * n);
-    if (!rc) rc = grow(&B.lists, &B.lists_cap, (uint64_t)W * list_cap);
+    rc = rr_grow(B, &B.cand, &B.cand_cap, cand.size());
+    if (!rc) rc = rr_grow(B, &B.want, &B.want_cap, tasks);
+    if (!rc) rc = rr_grow(B, &B.fetched, &B.fetched_cap, 2ull * n);
+    if (!rc) rc = rr_grow(B, &B.lists, &B.lists_cap, (uint64_t)W * list_cap);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(B.cand, cand.data(), cand.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(B.fetched, 0, 2ull * n * 8, e->main_s));
   }
-  void* sb[kMaxWorld];
-  void* rb[kMaxWorld];
-  uint64_t sn[kMaxWorld], rn[kMaxWorld];
+  Exchange x;  // the request lists, then the responses
   for (uint32_t j = 0; j < ncand; ++j) {
     uint32_t nreq[kMaxWorld] = {};
     uint64_t asked[kMaxWorld] = {};
@@ -151,7 +152,7 @@ int repair_remote_rounds(rmq_engine* e, const RepairArgs* a, uint32_t wgs, uint6
     }
     HIP_TRY(hipEventRecord(B.ev, e->main_s));
     HIP_TRY(hipStreamWaitEvent(r->xchg_s, B.ev, 0));
-    rc = swap_words(e, W, me);
+    rc = swap_words(e, W);
     if (rc) return rc;
     bool any = remain != 0;
     for (uint32_t q = 0; q < W; ++q) any = any || (q != me && hw[kRemoteWRecv + 2 * q + 1] != 0);
@@ -168,20 +169,18 @@ int repair_remote_rounds(rmq_engine* e, const RepairArgs* a, uint32_t wgs, uint6
       }
       // (a list that is not a header and whole requests is answered with nothing)
       const uint32_t nq = nb > kRemoteHdr && (nb - kRemoteHdr) % kRemoteReq == 0 ? (uint32_t)((nb - kRemoteHdr) / kRemoteReq) : 0u;
-      sn[q] = hw[kRemoteWSend + 2 * q];
-      rn[q] = nb;
-      sb[q] = B.lists + (uint64_t)q * list_cap;
+      x.peer(q, B.lists + (uint64_t)q * list_cap, hw[kRemoteWSend + 2 * q], nullptr, nb);
       S.in_off[q] = ro;
       S.w0[q] = nin;
-      ro += (nb + 15) & ~15ull;
+      ro += pad16(nb);
       nin += nq;
     }
     for (uint32_t q = W; q <= kMaxWorld; ++q) S.w0[q] = nin;
-    rc = grow(&B.rin, &B.rin_cap, std::max<uint64_t>(ro, 16));
-    if (!rc) rc = grow(&B.sv, &B.sv_cap, std::max<uint32_t>(nin, 1));
+    rc = rr_grow(B, &B.rin, &B.rin_cap, std::max<uint64_t>(ro, 16));
+    if (!rc) rc = rr_grow(B, &B.sv, &B.sv_cap, std::max<uint32_t>(nin, 1));
     if (rc) return rc;
-    for (uint32_t q = 0; q < W; ++q) rb[q] = B.rin + S.in_off[q];
-    rc = r->xport->exchange(sb, sn, rb, rn, r->xchg_s);
+    for (uint32_t q = 0; q < W; ++q) x.rb[q] = B.rin + S.in_off[q];
+    rc = x.post(r);
     if (rc) return rc;
     // 3. the serve: verdicts and span bytes, then (the response sized from them) directory and spans
     S.st = e->st;
@@ -204,11 +203,11 @@ int repair_remote_rounds(rmq_engine* e, const RepairArgs* a, uint32_t wgs, uint6
       const uint32_t nq = S.w0[q + 1] - S.w0[q];
       resp[q] = nq ? kRemoteHdr + (uint64_t)kRemoteDir * nq + hw[kRemoteWTot + 3 * q + 2] : 0;
       S.out_off[q] = oo;
-      oo += (resp[q] + 15) & ~15ull;
+      oo += pad16(resp[q]);
       served[0] += hw[kRemoteWTot + 3 * q];
       served[1] += hw[kRemoteWTot + 3 * q + 1];
     }
-    rc = grow(&B.out, &B.out_cap, std::max<uint64_t>(oo, 16));
+    rc = rr_grow(B, &B.out, &B.out_cap, std::max<uint64_t>(oo, 16));
     if (rc) return rc;
     S.out = B.out;
     launch_remote_serve_copy(S, r->xchg_s);
@@ -231,7 +230,7 @@ int repair_remote_rounds(rmq_engine* e, const RepairArgs* a, uint32_t wgs, uint6
       hw[kRemoteWSend + 2 * q] = resp[q];
       hw[kRemoteWSend + 2 * q + 1] = 0;
     }
-    rc = swap_words(e, W, me);
+    rc = swap_words(e, W);
     if (rc) return rc;
     // 5. the responses
     RemoteInstallArgs I{};
@@ -243,20 +242,18 @@ int repair_remote_rounds(rmq_engine* e, const RepairArgs* a, uint32_t wgs, uint6
         std::fprintf(stderr, "ripplemq: rank %u announced a repair response of %llu bytes\n", q, (unsigned long long)nb);
         return RMQ_EDEVICE;
       }
-      sn[q] = resp[q];
-      rn[q] = nb;
-      sb[q] = B.out + S.out_off[q];
+      x.peer(q, B.out + S.out_off[q], resp[q], nullptr, nb);
       I.in_off[q] = io;
       I.in_bytes[q] = nb;
       I.w0[q] = nout;
-      io += (nb + 15) & ~15ull;
+      io += pad16(nb);
       nout += nreq[q];
     }
     for (uint32_t q = W; q <= kMaxWorld; ++q) I.w0[q] = nout;
-    rc = grow(&B.in, &B.in_cap, std::max<uint64_t>(io, 16));
+    rc = rr_grow(B, &B.in, &B.in_cap, std::max<uint64_t>(io, 16));
     if (rc) return rc;
-    for (uint32_t q = 0; q < W; ++q) rb[q] = B.in + I.in_off[q];
-    rc = r->xport->exchange(sb, sn, rb, rn, r->xchg_s);
+    for (uint32_t q = 0; q < W; ++q) x.rb[q] = B.in + I.in_off[q];
+    rc = x.post(r);
     if (rc) return rc;
     HIP_TRY(hipEventRecord(B.ev, r->xchg_s));
     HIP_TRY(hipStreamWaitEvent(e->main_s, B.ev, 0));

@@ -24,44 +24,32 @@
 // that drive them): with a transport attached, launch groups close only when full, and control
 // calls that flush (rmq_sync, placement, leadership) are collective. At a drain the remaining
 // rounds are exchanged and their acks applied by a separate kernel.
-#include <chrono>
-#include <numeric>
-
 #include "engine_internal.hpp"
 
 namespace rmq {
 
 namespace {
 
+// A device buffer sized by the placement (zeroed), noted on the record that free_placed frees from,
+// also where the zeroing failed.
 template <typename T>
-int upload(T** d, const std::vector<T>& h) {
-  if (*d) hipFree(*d);
-  *d = nullptr;
-  int rc = dalloc(d, h.size());
-  if (rc || h.empty()) return rc;
-  HIP_TRY(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  return RMQ_OK;
+int placed_alloc(Replication* r, T** d, size_t count) {
+  const int rc = dalloc(d, count);
+  if (*d) r->placed.note(d);
+  return rc;
 }
 
-struct Entry {
-  uint64_t key;
-  uint32_t slot, p;
-  bool operator<(const Entry& o) const { return key != o.key ? key < o.key : slot < o.slot; }
-};
+template <typename T>
+int upload(Replication* r, T** d, const std::vector<T>& h) {
+  const int rc = placed_alloc(r, d, h.size());
+  return rc || h.empty() ? rc : write_words(*d, h);
+}
 
-uint64_t entry_hash(uint64_t key, uint32_t slot) { return key * RMQ_MAX_RF + slot; }
-
-void free_set_buffers(Replication* r) {
-  for (XchgSet& x : r->sets) {
-    void* bufs[] = {x.outbox, x.inbox, x.xe, x.xc, x.xc_n, x.sizes, x.ackout, x.ackin, x.rowv};
-    for (void* p : bufs)
-      if (p) hipFree(p);
-    x.outbox = x.inbox = nullptr;
-    x.xe = nullptr;
-    x.xc = nullptr;
-    x.xc_n = nullptr;
-    x.sizes = x.ackout = x.ackin = x.rowv = nullptr;
-  }
+// Every buffer of the placement before this one, the engine's two views of them included.
+void free_placed(rmq_engine* e) {
+  e->repl->placed.free_all();
+  e->st.outidx = nullptr;
+  e->st.eackv = nullptr;
 }
 
 }  // namespace
@@ -70,15 +58,16 @@ void free_set_buffers(Replication* r) {
 // start): next = the leader's log end, no request, no catch-up round. Engine drained.
 int reset_catchup(rmq_engine* e) {
   Replication* r = e->repl;
-  const size_t n = r->xo_p.size();
+  const std::vector<uint32_t>& xo_p = r->lists.xo_p;
+  const size_t n = xo_p.size();
   if (!n) return RMQ_OK;
   const uint32_t P = e->cfg.num_partitions;
   std::vector<uint64_t> leo(P), used(P), nx(2 * n);
   HIP_TRY(hipMemcpy(leo.data(), e->st.leo, P * 8ull, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(used.data(), e->st.used, P * 8ull, hipMemcpyDeviceToHost));
   for (size_t k = 0; k < n; ++k) {
-    nx[2 * k] = leo[r->xo_p[k]];
-    nx[2 * k + 1] = used[r->xo_p[k]];
+    nx[2 * k] = leo[xo_p[k]];
+    nx[2 * k + 1] = used[xo_p[k]];
   }
   HIP_TRY(hipMemcpy(r->d_xnext, nx.data(), nx.size() * 8, hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(r->d_xreq, 0, n * 32));
@@ -88,25 +77,129 @@ int reset_catchup(rmq_engine* e) {
 
 namespace {
 
+// The two fixed-size words of every entry, both ways: to peer q those of send's entries for q
+// (grouped by sstart), from q those of recv's entries (grouped by rstart).
+Exchange entry_swap(const Replication* r, uint64_t* send, const std::vector<uint32_t>& sstart, uint64_t* recv,
+                    const std::vector<uint32_t>& rstart) {
+  Exchange x;
+  for (uint32_t q = 0; q < r->world; ++q) {
+    const EntrySpan s = entry_span(sstart, q), g = entry_span(rstart, q);
+    x.peer(q, send + s.word, q == r->rank ? 0 : s.bytes, recv + g.word, q == r->rank ? 0 : g.bytes);
+  }
+  return x;
+}
+
+// The follower ingest of the round in set x, laid out as l.
+IngestArgs ingest_args(const rmq_engine* e, const XchgSet& x, const RoundLayout& l) {
+  const Replication* r = e->repl;
+  IngestArgs a{};
+  a.st = e->st;
+  a.sets[0] = e->sets[0];
+  a.sets[1] = e->sets[1];
+  a.inbox = x.inbox;
+  std::copy_n(l.region, kMaxWorld, a.region);
+  std::copy_n(l.rn, kMaxWorld, a.rbytes);
+  std::copy_n(l.task0, kMaxWorld + 1, a.task0);
+  a.xi_p = r->d_xi_p;
+  a.xi_slot = r->d_xi_slot;
+  a.xi_start = r->d_xi_start;
+  a.world = r->world;
+  a.rank = r->rank;
+  a.n_in = (uint32_t)r->lists.xi_p.size();
+  a.C = e->cfg.max_consumers;
+  a.bad = r->d_bad;
+  a.acc = r->d_acc;
+  a.base = r->d_base;
+  a.cdesc = r->d_cdesc;
+  a.ackout = x.ackout;
+  a.items = r->d_items;
+  constexpr uint32_t NW = 1 + kMaxWorld;  // rounds alternate halves of d_nitems
+  uint32_t* cur = r->d_nitems + (r->nitems_par ? NW : 0u);
+  a.n_items = cur;
+  a.insane = cur + 1;
+  a.n_items_next = r->d_nitems + (r->nitems_par ? 0u : NW);
+  a.keysum_in = r->d_keysum_in;
+  a.items_cap = (uint32_t)r->items_cap;
+  a.items_grid = l.items;
+  a.crc = e->d_crc;
+  a.counters = r->d_counters;
+  a.stamp = x.round + 1ull;  // (rmq_leader_silent's clock: rounds ingested)
+  return a;
+}
+
+// The plan of stage 2's group in set x (PipeArgs::xp2; the acks it reads: repl_before_launch).
+XPlanArgs xplan_args(const rmq_engine* e, const XchgSet& x) {
+  const Replication* r = e->repl;
+  XPlanArgs a{};
+  a.xo_p = r->d_xo_p;
+  a.xo_slot = r->d_xo_slot;
+  a.xo_start = r->d_xo_start;
+  a.keysum = r->d_keysum;
+  a.world = r->world;
+  a.rank = r->rank;
+  a.n_out = (uint32_t)r->lists.xo_p.size();
+  a.C = e->cfg.max_consumers;
+  a.count = x.count;
+  a.xe = x.xe;
+  a.outbox = x.outbox;
+  a.sizes = x.sizes;
+  a.round = x.round;
+  a.reserve = r->reserve;
+  a.xnext = r->d_xnext;
+  a.xreq = r->d_xreq;
+  a.xcu = r->d_xcu;
+  a.xdec = r->d_xdec;
+  a.xtot = r->d_xtot;
+  a.dflag = r->d_dflag;
+  // the commit the round carries: the slot of the launch before this one (launch_seq not yet advanced)
+  a.csnap = e->st.csnap + (size_t)(e->launch_seq & 1ull) * e->cfg.num_partitions;
+  a.dirty = e->st.cdirty;
+  a.rowv = x.rowv;
+  a.xc = x.xc;
+  a.xc_n = x.xc_n;
+  a.counters = r->d_counters + 4;
+  a.dcap = r->dcap;
+  return a;
+}
+
+NoticeArgs notice_args(const rmq_engine* e) {
+  const Replication* r = e->repl;
+  NoticeArgs a{};
+  a.st = e->st;
+  a.sets[0] = e->sets[0];
+  a.sets[1] = e->sets[1];
+  a.xo_p = r->d_xo_p;
+  a.out = r->d_nout;
+  a.xi_p = r->d_xi_p;
+  a.in = r->d_nin;
+  a.n_out = (uint32_t)r->lists.xo_p.size();
+  a.n_in = (uint32_t)r->lists.xi_p.size();
+  a.stamp = r->stamp;
+  return a;
+}
+
+AckApplyArgs ack_apply_args(const rmq_engine* e, const XchgSet& x) {
+  AckApplyArgs a{};
+  a.st = e->st;
+  a.outidx = e->repl->d_outidx;
+  a.ackin = x.ackin;
+  a.rowv = x.rowv;
+  a.xreq = e->repl->d_xreq;
+  a.acks_round = x.round;
+  return a;
+}
+
 // Post the {region bytes, records} swap of the group in set s (after its stage-2 launch). drop: the
 // leader sends no region this round; lost: bit q, the region to q is lost (rmq_fault_isolate).
 int post_sizes(rmq_engine* e, uint32_t s, bool drop, uint32_t lost) {
   Replication* r = e->repl;
   XchgSet& x = r->sets[s];
   const uint32_t W = r->world;
-  void* sb[kMaxWorld];
-  void* rb[kMaxWorld];
-  uint64_t n16[kMaxWorld];
-  for (uint32_t q = 0; q < W; ++q) {
-    sb[q] = x.sizes + 2 * q;
-    rb[q] = x.sizes + 2 * W + 2 * q;
-    n16[q] = q == r->rank ? 0 : 16;
-  }
   HIP_TRY(hipStreamWaitEvent(r->xchg_s, x.ev_s2, 0));
   if (drop) HIP_TRY(hipMemsetAsync(x.sizes, 0, 2ull * W * 8, r->xchg_s));  // no region to anyone
   for (uint32_t q = 0; q < W && !drop; ++q)
     if ((lost >> q) & 1u) HIP_TRY(hipMemsetAsync(x.sizes + 2 * q, 0, 16, r->xchg_s));
-  int rc = r->xport->exchange(sb, n16, rb, n16, r->xchg_s);
+  int rc = fixed_swap(r, x.sizes, x.sizes + 2 * W, 2, 16).post(r);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(x.h_sizes, x.sizes, 4ull * W * 8, hipMemcpyDeviceToHost, r->xchg_s));
   HIP_TRY(hipEventRecord(x.ev_sz, r->xchg_s));
@@ -127,91 +220,37 @@ int post_round(rmq_engine* e, uint32_t s) {
     r->host_waits++;
     r->host_wait_ns += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
   }
-  const uint64_t* hs = x.h_sizes;  // [q]: {send bytes, send records}, then [W + q]: {recv bytes, recv records}
-  void* sb[kMaxWorld];
-  void* rb[kMaxWorld];
-  uint64_t sn[kMaxWorld], rn[kMaxWorld];
-  IngestArgs a{};
-  uint64_t ro = 0, smax = 0;
-  uint32_t tasks = 0;
-  const uint64_t kvr = verify_records_per_task();
-  for (uint32_t q = 0; q < W; ++q) {
-    sn[q] = q == me ? 0 : hs[2 * q];
-    rn[q] = q == me ? 0 : hs[2 * W + 2 * q];
-    sb[q] = x.outbox + (uint64_t)q * r->dcap;
-    rb[q] = x.inbox + ro;
-    a.region[q] = ro;
-    a.rbytes[q] = rn[q];
-    a.task0[q] = tasks;
-    tasks += (uint32_t)((rn[q] ? hs[2 * W + 2 * q + 1] : 0) + kvr - 1) / kvr;
-    smax = std::max(smax, sn[q]);
-    ro += (rn[q] + 15) & ~15ull;
-  }
-  a.task0[W] = tasks;
-  if (smax > r->dcap || ro > r->in_cap) {
+  const RoundLayout l = plan_round(x.h_sizes, W, me, r->dcap, verify_records_per_task(), r->items_cap,
+                                   r->lists.xi_p.size(), kCopyChunk);
+  if (l.smax > r->dcap || l.ro > r->in_cap) {
     std::fprintf(stderr, "ripplemq: replication round exceeds its buffers (%llu/%llu out, %llu/%llu in)\n",
-                 (unsigned long long)smax, (unsigned long long)r->dcap, (unsigned long long)ro,
+                 (unsigned long long)l.smax, (unsigned long long)r->dcap, (unsigned long long)l.ro,
                  (unsigned long long)r->in_cap);
     return RMQ_EDEVICE;
   }
-  // copy work items: at most one per 16 KiB of received region bytes plus one per entry
-  const uint32_t items = (uint32_t)std::min<uint64_t>(r->items_cap, ro / kCopyChunk + W + r->xi_p.size());
+  Exchange regions;
+  for (uint32_t q = 0; q < W; ++q) regions.peer(q, x.outbox + l.soff[q], l.sn[q], x.inbox + l.region[q], l.rn[q]);
   HIP_TRY(hipStreamWaitEvent(r->xchg_s, x.ev_s3, 0));
   for (uint32_t q = 0; q < W; ++q)  // rmq_fault_corrupt
-    if (r->flip[q] && sn[q]) {
-      launch_flip(static_cast<uint8_t*>(sb[q]), sn[q], r->flip_at[q], r->xchg_s);
+    if (r->flip[q] && l.sn[q]) {
+      launch_flip(static_cast<uint8_t*>(regions.sb[q]), l.sn[q], r->flip_at[q], r->xchg_s);
       r->flip[q] = false;
     }
-  int rc = r->xport->exchange(sb, sn, rb, rn, r->xchg_s);
+  int rc = regions.post(r);
   if (rc) return rc;
-  a.st = e->st;
-  a.sets[0] = e->sets[0];
-  a.sets[1] = e->sets[1];
-  a.inbox = x.inbox;
-  a.xi_p = r->d_xi_p;
-  a.xi_slot = r->d_xi_slot;
-  a.xi_start = r->d_xi_start;
-  a.world = W;
-  a.rank = me;
-  a.n_in = (uint32_t)r->xi_p.size();
-  a.C = e->cfg.max_consumers;
-  a.bad = r->d_bad;
-  a.acc = r->d_acc;
-  a.base = r->d_base;
-  a.cdesc = r->d_cdesc;
-  a.ackout = x.ackout;
-  a.items = r->d_items;
-  {
-    constexpr uint32_t NW = 1 + kMaxWorld;
-    uint32_t* cur = r->d_nitems + (r->nitems_par ? NW : 0u);
-    a.n_items = cur;
-    a.insane = cur + 1;
-    a.n_items_next = r->d_nitems + (r->nitems_par ? 0u : NW);
-  }
-  a.keysum_in = r->d_keysum_in;
-  a.items_cap = (uint32_t)r->items_cap;
-  a.items_grid = items;
-  a.crc = e->d_crc;
-  a.counters = r->d_counters;
-  a.stamp = x.round + 1ull;  // (rmq_leader_silent's clock: rounds ingested)
+  const IngestArgs a = ingest_args(e, x, l);
   if (a.stamp > r->stamp) r->stamp = a.stamp;
   r->stamp_time[a.stamp % 64] = std::chrono::steady_clock::now();
-  launch_ingest(a, tasks, items, e->knob.verify_wgs, r->xchg_s);
+  launch_ingest(a, l.tasks, l.items, e->knob.verify_wgs, r->xchg_s);
   if (a.n_in) r->nitems_par ^= 1u;  // (prepare ran: it cleared the other half)
   HIP_TRY(hipGetLastError());
   // acks: {log end | status, position} of every in entry back to its leader, fixed sizes both ways
-  for (uint32_t q = 0; q < W; ++q) {
-    sn[q] = q == me ? 0 : 16ull * (r->xi_start[q + 1] - r->xi_start[q]);
-    rn[q] = q == me ? 0 : 16ull * (r->xo_start[q + 1] - r->xo_start[q]);
-    sb[q] = x.ackout + 2ull * r->xi_start[q];
-    rb[q] = x.ackin + 2ull * r->xo_start[q];
-  }
-  rc = r->xport->exchange(sb, sn, rb, rn, r->xchg_s);
+  rc = entry_swap(r, x.ackout, r->lists.xi_start, x.ackin, r->lists.xo_start).post(r);
   if (rc) return rc;
   HIP_TRY(hipEventRecord(x.ev_x, r->xchg_s));
   r->rounds++;
-  for (uint32_t q = 0; q < W; ++q) r->bytes_sent += q == me ? 0 : hs[2 * q];
-  r->bytes_recv += ro;
+  for (uint32_t q = 0; q < W; ++q) r->bytes_sent += l.sn[q];
+  r->bytes_recv += l.ro;
   r->last_set = s;
   r->acking.push_back(s);
   return RMQ_OK;
@@ -243,6 +282,7 @@ int repl_attach(rmq_engine* e, Transport* t) {
   }
   int rc = dalloc(&r->d_counters, 7);
   if (!rc) rc = dalloc(&r->d_lastg, e->cfg.num_partitions);
+  if (!rc) rc = dalloc(&r->d_shake, 8ull * kMaxWorld);
   if (!rc && !e->st.csnap) rc = owned_dalloc(e, &e->st.csnap, 2ull * e->cfg.num_partitions);
   if (rc) return rc;
   {
@@ -258,7 +298,8 @@ void repl_free(rmq_engine* e) {
   Replication* r = e->repl;
   if (!r) return;
   if (r->xchg_s) hipStreamSynchronize(r->xchg_s);
-  free_set_buffers(r);
+  free_placed(e);
+  // what repl_attach made
   for (XchgSet& x : r->sets) {
     hipEvent_t evs[] = {x.ev_s2, x.ev_s3, x.ev_sz, x.ev_x};
     for (hipEvent_t v : evs)
@@ -266,14 +307,9 @@ void repl_free(rmq_engine* e) {
     if (x.count) hipFree(x.count);
     if (x.h_sizes) hipHostFree(x.h_sizes);
   }
-  void* bufs[] = {r->d_xo_p, r->d_xo_slot, r->d_xo_start, r->d_keysum, r->d_keysum_in, r->d_outidx, r->d_xi_p, r->d_xi_slot,
-                  r->d_xi_start, r->d_bad, r->d_acc, r->d_base, r->d_cdesc, r->d_items, r->d_nitems, r->d_counters,
-                  r->d_xnext, r->d_xreq, r->d_xcu, r->d_xdec, r->d_xtot, r->d_dflag, r->d_lastg,
-                  r->d_nout, r->d_nin, r->d_eackv};
-  for (void* p : bufs)
-    if (p) hipFree(p);
-  e->st.outidx = nullptr;
-  e->st.eackv = nullptr;
+  if (r->d_counters) hipFree(r->d_counters);
+  if (r->d_lastg) hipFree(r->d_lastg);
+  if (r->d_shake) hipFree(r->d_shake);
   if (r->ev_notice) hipEventDestroy(r->ev_notice);
   if (r->xchg_s) hipStreamDestroy(r->xchg_s);
   delete r->xport;
@@ -281,192 +317,155 @@ void repl_free(rmq_engine* e) {
   e->repl = nullptr;
 }
 
-// Out / in lists from the placement, the collective consistency check, and the round buffers.
-// Called with the engine drained, by every rank.
-int repl_set_lists(rmq_engine* e) {
-  Replication* r = e->repl;
-  const uint32_t P = e->cfg.num_partitions, RF = e->cfg.replication_factor, W = r->world, me = r->rank;
-  std::vector<std::vector<Entry>> out(W), in(W);
-  int bad = RMQ_OK;
-  for (uint32_t p = 0; p < P; ++p) {
-    const uint32_t* rk = &e->ranks[(size_t)p * RF];
-    const uint32_t lead = rk[e->leader_slot[p]];
-    uint32_t remote = 0;
-    for (uint32_t s = 0; s < RF; ++s) {
-      if (rk[s] >= W) bad = RMQ_EINVAL;
-      else if (lead == me && rk[s] != me) {
-        out[rk[s]].push_back({e->key[p], s, p});
-        ++remote;
-      } else if (lead != me && rk[s] == me && lead < W) {
-        in[lead].push_back({e->key[p], s, p});
-      }
-    }
-    if (remote > kMaxRemote) bad = RMQ_EINVAL;
-  }
-  r->xo_p.clear();
-  r->xo_slot.clear();
-  r->xi_p.clear();
-  r->xi_slot.clear();
-  r->xo_start.assign(W + 1, 0);
-  r->xi_start.assign(W + 1, 0);
-  r->keysum.assign(W, 0);
-  std::vector<uint64_t> keysum_in(W, 0);
-  std::vector<uint32_t> outidx((size_t)P * RF, ~0u);
+namespace {
+
+// Step 1 of repl_set_lists: the out / in lists of the engine's placement, into the host mirrors.
+void plan_placement(rmq_engine* e) {
+  Placement pl;
+  pl.P = e->cfg.num_partitions, pl.RF = e->cfg.replication_factor, pl.W = e->repl->world, pl.me = e->repl->rank;
+  pl.ranks = e->ranks.data(), pl.leader_slot = e->leader_slot.data(), pl.key = e->key.data();
+  e->repl->lists = plan_lists(pl, kMaxRemote, RMQ_MAX_RF);
+}
+
+// Step 2, the handshake: what I send to q must be what q expects from me, and every rank learns
+// whether all pairs agree (two exchanges, so no rank starts rounds that another refuses).
+int handshake(Replication* r) {
+  const ReplLists& l = r->lists;
+  const uint32_t W = r->world, me = r->rank;
+  uint64_t* d = r->d_shake;
+  std::vector<uint64_t> h(8ull * W, 0);  // [q]: send {entries, keysum}; [W + q]: recv; [2W..] verdicts
   for (uint32_t q = 0; q < W; ++q) {
-    std::sort(out[q].begin(), out[q].end());
-    std::sort(in[q].begin(), in[q].end());
-    r->xo_start[q] = (uint32_t)r->xo_p.size();
-    for (const Entry& x : out[q]) {
-      outidx[(size_t)x.p * RF + x.slot] = (uint32_t)r->xo_p.size();
-      r->xo_p.push_back(x.p);
-      r->xo_slot.push_back(x.slot);
-      r->keysum[q] += entry_hash(x.key, x.slot);
-    }
-    r->xi_start[q] = (uint32_t)r->xi_p.size();
-    for (const Entry& x : in[q]) {
-      r->xi_p.push_back(x.p);
-      r->xi_slot.push_back(x.slot);
-      keysum_in[q] += entry_hash(x.key, x.slot);
-    }
+    h[2 * q] = l.xo_start[q + 1] - l.xo_start[q];
+    h[2 * q + 1] = l.keysum[q];
   }
-  r->xo_start[W] = (uint32_t)r->xo_p.size();
-  r->xi_start[W] = (uint32_t)r->xi_p.size();
-  // handshake: what I send to q must be what q expects from me, and every rank learns whether all
-  // pairs agree (two exchanges, so no rank starts rounds that another refuses)
-  {
-    std::vector<uint64_t> h(8ull * W, 0);  // [q]: send {entries, keysum}; [W + q]: recv; [2W..] verdicts
-    for (uint32_t q = 0; q < W; ++q) {
-      h[2 * q] = r->xo_start[q + 1] - r->xo_start[q];
-      h[2 * q + 1] = r->keysum[q];
-    }
-    uint64_t* d = nullptr;
-    int rc = dalloc(&d, h.size());
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(d, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-    void* sb[kMaxWorld];
-    void* rb[kMaxWorld];
-    uint64_t n[kMaxWorld];
-    for (uint32_t q = 0; q < W; ++q) {
-      sb[q] = d + 2 * q;
-      rb[q] = d + 2 * W + 2 * q;
-      n[q] = q == me ? 0 : 16;
-    }
-    rc = r->xport->exchange(sb, n, rb, n, r->xchg_s);
-    if (!rc) rc = hip_fail(hipStreamSynchronize(r->xchg_s));
-    if (!rc) rc = hip_fail(hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost));
-    uint64_t verdict = bad ? 1 : 0;
-    for (uint32_t q = 0; q < W && !rc; ++q)
-      if (q != me && (h[2 * W + 2 * q] != r->xi_start[q + 1] - r->xi_start[q] || h[2 * W + 2 * q + 1] != keysum_in[q]))
-        verdict = 1;
-    for (uint32_t q = 0; q < W; ++q) h[4 * W + q] = verdict;
-    if (!rc) rc = hip_fail(hipMemcpy(d + 4 * W, h.data() + 4 * W, 8ull * W, hipMemcpyHostToDevice));
-    for (uint32_t q = 0; q < W; ++q) {
-      sb[q] = d + 4 * W + q;
-      rb[q] = d + 5 * W + q;
-      n[q] = q == me ? 0 : 8;
-    }
-    if (!rc) rc = r->xport->exchange(sb, n, rb, n, r->xchg_s);
-    if (!rc) rc = hip_fail(hipStreamSynchronize(r->xchg_s));
-    if (!rc) rc = hip_fail(hipMemcpy(h.data() + 5 * W, d + 5 * W, 8ull * W, hipMemcpyDeviceToHost));
-    hipFree(d);
-    if (rc) return rc;
-    for (uint32_t q = 0; q < W; ++q) verdict |= q != me ? h[5 * W + q] : 0;
-    if (verdict) {
-      std::fprintf(stderr, "ripplemq: replica placement differs between ranks (rank %u)\n", me);
-      return RMQ_EINVAL;
-    }
-  }
-  int rc = upload(&r->d_xo_p, r->xo_p);
-  if (!rc) rc = upload(&r->d_xo_slot, r->xo_slot);
-  if (!rc) rc = upload(&r->d_xo_start, r->xo_start);
-  if (!rc) rc = upload(&r->d_keysum, r->keysum);
-  if (!rc) rc = upload(&r->d_keysum_in, keysum_in);
-  if (!rc) rc = upload(&r->d_outidx, outidx);
-  if (!rc) rc = upload(&r->d_xi_p, r->xi_p);
-  if (!rc) rc = upload(&r->d_xi_slot, r->xi_slot);
-  if (!rc) rc = upload(&r->d_xi_start, r->xi_start);
-  const size_t n_in = std::max<size_t>(1, r->xi_p.size()), n_out = std::max<size_t>(1, r->xo_p.size());
-  if (!rc) rc = upload(&r->d_bad, std::vector<uint32_t>(n_in, 0u));
-  if (!rc) rc = upload(&r->d_acc, std::vector<uint32_t>(n_in, 0u));
-  if (!rc) rc = upload(&r->d_base, std::vector<uint64_t>(2 * n_in, 0ull));
-  if (!rc) rc = upload(&r->d_cdesc, std::vector<uint64_t>(4 * n_in, 0ull));
-  if (!rc) rc = upload(&r->d_xnext, std::vector<uint64_t>(2 * n_out, 0ull));
-  if (!rc) rc = upload(&r->d_xreq, std::vector<uint64_t>(4 * n_out, 0ull));
-  if (!rc) rc = upload(&r->d_xcu, std::vector<uint64_t>(n_out, 0ull));
-  if (!rc) rc = upload(&r->d_dflag, std::vector<uint32_t>(W, 0u));
-  if (!rc) rc = upload(&r->d_nout, std::vector<uint64_t>(2 * n_out, 0ull));
-  if (!rc) rc = upload(&r->d_nin, std::vector<uint64_t>(2 * n_in, 0ull));
-  if (r->d_xdec) hipFree(r->d_xdec);
-  if (r->d_xtot) hipFree(r->d_xtot);
-  r->d_xdec = nullptr;
-  r->d_xtot = nullptr;
-  if (!rc) rc = dalloc(&r->d_xdec, n_out);
-  if (!rc) rc = dalloc(&r->d_xtot, n_out);
+  int rc = write_words(d, h);
+  if (!rc) rc = fixed_swap(r, d, d + 2 * W, 2, 16).post(r);
+  if (!rc) rc = hip_fail(hipStreamSynchronize(r->xchg_s));
+  if (!rc) rc = read_words(h, d);
   if (rc) return rc;
-  // round buffers (FORMAT.md §9 bounds): a record is at most 31 + L bytes in the log, sent once per
-  // remote slot, plus an 8-byte table slot; the catch-up reserve of a destination is one such
-  // round bound (ro_catchup_reserve in the oracle); per region a header, a directory, table padding
-  // and the consumer-offset rows
-  const uint64_t G = e->group_max, NR = e->cfg.max_batch_records, MB = e->cfg.max_batch_bytes;
-  const uint64_t rec = G * (39ull * NR + MB), C = e->cfg.max_consumers;
-  uint32_t max_remote = 0;
-  for (uint32_t p = 0; p < P; ++p) {
-    uint32_t k = 0;
-    for (uint32_t s = 0; s < RF; ++s) k += outidx[(size_t)p * RF + s] != ~0u;
-    max_remote = std::max(max_remote, k);
+  uint64_t verdict = l.bad ? 1 : 0;
+  for (uint32_t q = 0; q < W; ++q)
+    if (q != me && (h[2 * W + 2 * q] != l.xi_start[q + 1] - l.xi_start[q] || h[2 * W + 2 * q + 1] != l.keysum_in[q]))
+      verdict = 1;
+  for (uint32_t q = 0; q < W; ++q) h[4 * W + q] = verdict;
+  rc = write_words(d + 4 * W, h.data() + 4 * W, W);
+  if (!rc) rc = fixed_swap(r, d + 4 * W, d + 5 * W, 1, 8).post(r);
+  if (!rc) rc = hip_fail(hipStreamSynchronize(r->xchg_s));
+  if (!rc) rc = read_words(h.data() + 5 * W, d + 5 * W, W);
+  if (rc) return rc;
+  for (uint32_t q = 0; q < W; ++q) verdict |= q != me ? h[5 * W + q] : 0;
+  if (verdict) {
+    std::fprintf(stderr, "ripplemq: replica placement differs between ranks (rank %u)\n", me);
+    return RMQ_EINVAL;
   }
-  const uint64_t per_entry = kDirEntry + 16 + 8 * C;
-  r->reserve = rec;
-  r->dcap = ((uint64_t)max_remote * rec + r->reserve + kRegionHdr + 16 + per_entry * n_out + 255) & ~255ull;
-  r->out_cap = (uint64_t)W * r->dcap;
-  r->in_cap = (uint64_t)(W - 1) * ((uint64_t)(RF - 1) * rec + r->reserve + kRegionHdr + 32) + per_entry * n_in;
-  r->items_cap = r->in_cap / kCopyChunk + W + n_in;
-  if (r->d_items) hipFree(r->d_items);
-  if (r->d_nitems) hipFree(r->d_nitems);
-  r->d_items = nullptr;
-  r->d_nitems = nullptr;
-  rc = dalloc(&r->d_items, 2 * r->items_cap);
-  if (!rc) rc = dalloc(&r->d_nitems, 2 * (1 + kMaxWorld));  // both halves zero
+  return RMQ_OK;
+}
+
+// The FORMAT.md §9 bounds of the placement's round buffers.
+ReplBounds placement_bounds(const rmq_engine* e) {
+  const ReplLists& l = e->repl->lists;
+  BoundsShape s;
+  s.group_max = e->group_max, s.max_batch_records = e->cfg.max_batch_records;
+  s.max_batch_bytes = e->cfg.max_batch_bytes, s.max_consumers = e->cfg.max_consumers;
+  s.W = e->repl->world, s.RF = e->cfg.replication_factor, s.max_remote = l.max_remote;
+  s.n_out = l.xo_p.size(), s.n_in = l.xi_p.size();
+  return plan_bounds(s, {kRegionHdr, kDirEntry, kCopyChunk});
+}
+
+// Step 3: the lists on the device and the per-entry state, zeroed.
+int upload_lists(Replication* r, const ReplBounds& b) {
+  const ReplLists& l = r->lists;
+  int rc = upload(r, &r->d_xo_p, l.xo_p);
+  if (!rc) rc = upload(r, &r->d_xo_slot, l.xo_slot);
+  if (!rc) rc = upload(r, &r->d_xo_start, l.xo_start);
+  if (!rc) rc = upload(r, &r->d_keysum, l.keysum);
+  if (!rc) rc = upload(r, &r->d_keysum_in, l.keysum_in);
+  if (!rc) rc = upload(r, &r->d_outidx, l.outidx);
+  if (!rc) rc = upload(r, &r->d_xi_p, l.xi_p);
+  if (!rc) rc = upload(r, &r->d_xi_slot, l.xi_slot);
+  if (!rc) rc = upload(r, &r->d_xi_start, l.xi_start);
+  if (!rc) rc = placed_alloc(r, &r->d_bad, b.n_in);
+  if (!rc) rc = placed_alloc(r, &r->d_acc, b.n_in);
+  if (!rc) rc = placed_alloc(r, &r->d_base, 2 * b.n_in);
+  if (!rc) rc = placed_alloc(r, &r->d_cdesc, 4 * b.n_in);
+  if (!rc) rc = placed_alloc(r, &r->d_xnext, 2 * b.n_out);
+  if (!rc) rc = placed_alloc(r, &r->d_xreq, 4 * b.n_out);
+  if (!rc) rc = placed_alloc(r, &r->d_xcu, b.n_out);
+  if (!rc) rc = placed_alloc(r, &r->d_dflag, r->world);
+  if (!rc) rc = placed_alloc(r, &r->d_nout, 2 * b.n_out);
+  if (!rc) rc = placed_alloc(r, &r->d_nin, 2 * b.n_in);
+  if (!rc) rc = placed_alloc(r, &r->d_xdec, b.n_out);
+  if (!rc) rc = placed_alloc(r, &r->d_xtot, b.n_out);
+  return rc;
+}
+
+// Step 4: the bounds post_round answers RMQ_EDEVICE against, the copy items and every set's buffers.
+int alloc_round_buffers(Replication* r, const ReplBounds& b) {
+  r->reserve = b.reserve;
+  r->dcap = b.dcap;
+  r->out_cap = b.out_cap;
+  r->in_cap = b.in_cap;
+  r->items_cap = b.items_cap;
+  int rc = placed_alloc(r, &r->d_items, 2 * b.items_cap);
+  if (!rc) rc = placed_alloc(r, &r->d_nitems, 2 * (1 + kMaxWorld));  // both halves zero
   r->nitems_par = 0;
-  if (rc) return rc;
-  free_set_buffers(r);
   for (XchgSet& x : r->sets) {
-    rc = dalloc(&x.outbox, r->out_cap);
-    if (!rc) rc = dalloc(&x.inbox, r->in_cap);
-    if (!rc) rc = dalloc(&x.xe, n_out);
-    if (!rc) rc = dalloc(&x.xc, n_out);
-    if (!rc) rc = dalloc(&x.xc_n, 2);
-    if (!rc) rc = dalloc(&x.sizes, 4ull * W);
-    if (!rc) rc = dalloc(&x.ackout, 2 * n_in);
-    if (!rc) rc = dalloc(&x.ackin, 2 * n_out);
-    if (!rc) rc = dalloc(&x.rowv, n_out);
-    if (rc) return rc;
+    if (!rc) rc = placed_alloc(r, &x.outbox, b.out_cap);
+    if (!rc) rc = placed_alloc(r, &x.inbox, b.in_cap);
+    if (!rc) rc = placed_alloc(r, &x.xe, b.n_out);
+    if (!rc) rc = placed_alloc(r, &x.xc, b.n_out);
+    if (!rc) rc = placed_alloc(r, &x.xc_n, 2);
+    if (!rc) rc = placed_alloc(r, &x.sizes, 4ull * r->world);
+    if (!rc) rc = placed_alloc(r, &x.ackout, 2 * b.n_in);
+    if (!rc) rc = placed_alloc(r, &x.ackin, 2 * b.n_out);
+    if (!rc) rc = placed_alloc(r, &x.rowv, b.n_out);
   }
-  // consumer-offset rows: the followers acknowledge them afresh under the new lists (the rows of
-  // every led partition with committed offsets go out with the next round) and every partition's
-  // row quorum is recomputed (pending offset tickets wait for those rounds' acks)
-  if (r->d_eackv) hipFree(r->d_eackv);
-  r->d_eackv = nullptr;
-  rc = dalloc(&r->d_eackv, n_out);
+  return rc;
+}
+
+// Step 5, the consumer-offset rows: the followers acknowledge them afresh under the new lists (the
+// rows of every led partition with committed offsets go out with the next round) and every
+// partition's row quorum is recomputed (pending offset tickets wait for those rounds' acks).
+int rearm_consumer_rows(rmq_engine* e, const ReplBounds& b) {
+  Replication* r = e->repl;
+  const uint32_t P = e->cfg.num_partitions;
+  int rc = placed_alloc(r, &r->d_eackv, b.n_out);
   if (rc) return rc;
   e->st.outidx = r->d_outidx;
   e->st.eackv = r->d_eackv;
-  {
-    std::vector<uint32_t> dirty(P, 0u);
-    bool any = false;
-    for (uint32_t p = 0; p < P; ++p)
-      if (e->is_leader[p] && e->cver[p]) dirty[p] = 1u, any = true;
-    if (any) {
-      std::vector<uint32_t> cur(P);
-      HIP_TRY(hipMemcpy(cur.data(), e->st.cdirty, P * 4ull, hipMemcpyDeviceToHost));
-      for (uint32_t p = 0; p < P; ++p) dirty[p] |= cur[p];
-      HIP_TRY(hipMemcpy(e->st.cdirty, dirty.data(), P * 4ull, hipMemcpyHostToDevice));
-    }
+  std::vector<uint32_t> dirty(P, 0u);
+  bool any = false;
+  for (uint32_t p = 0; p < P; ++p)
+    if (e->is_leader[p] && e->cver[p]) dirty[p] = 1u, any = true;
+  if (any) {
+    std::vector<uint32_t> cur(P);
+    rc = read_words(cur, e->st.cdirty);
+    for (uint32_t p = 0; p < P; ++p) dirty[p] |= cur[p];
+    if (!rc) rc = write_words(e->st.cdirty, dirty);
+    if (rc) return rc;
   }
   launch_row_quorum_all(e->st, e->main_s);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(e->main_s));
-  return reset_catchup(e);
+  return RMQ_OK;
+}
+
+}  // namespace
+
+// Out / in lists from the placement, the collective consistency check, and the round buffers.
+// Called with the engine drained, by every rank. A refused handshake leaves the host mirrors
+// replaced and every device buffer (with DevState::outidx / eackv) the old placement's.
+int repl_set_lists(rmq_engine* e) {
+  Replication* r = e->repl;
+  plan_placement(e);
+  int rc = handshake(r);
+  if (rc) return rc;
+  free_placed(e);
+  const ReplBounds b = placement_bounds(e);
+  rc = upload_lists(r, b);
+  if (!rc) rc = alloc_round_buffers(r, b);
+  if (!rc) rc = rearm_consumer_rows(e, b);
+  return rc ? rc : reset_catchup(e);
 }
 
 void repl_pipe_args(rmq_engine* e, PipeArgs& a, const GroupFlight* s2, const GroupFlight* s3) {
@@ -476,39 +475,9 @@ void repl_pipe_args(rmq_engine* e, PipeArgs& a, const GroupFlight* s2, const Gro
   // every rank numbers every round (the follower side stamps its ingest with it), also one that
   // leads nothing with a remote replica
   if (s2) r->sets[s2->set].round = r->planned++;
-  if (r->xo_p.empty()) return;        // nothing led here has a remote replica
+  if (r->lists.xo_p.empty()) return;  // nothing led here has a remote replica
   a.outidx = r->d_outidx;
-  if (s2) {
-    XchgSet& x = r->sets[s2->set];
-    a.xp2.xo_p = r->d_xo_p;
-    a.xp2.xo_slot = r->d_xo_slot;
-    a.xp2.xo_start = r->d_xo_start;
-    a.xp2.keysum = r->d_keysum;
-    a.xp2.world = r->world;
-    a.xp2.rank = r->rank;
-    a.xp2.n_out = (uint32_t)r->xo_p.size();
-    a.xp2.C = e->cfg.max_consumers;
-    a.xp2.count = x.count;
-    a.xp2.xe = x.xe;
-    a.xp2.outbox = x.outbox;
-    a.xp2.sizes = x.sizes;
-    a.xp2.round = x.round;
-    a.xp2.reserve = r->reserve;
-    a.xp2.xnext = r->d_xnext;
-    a.xp2.xreq = r->d_xreq;
-    a.xp2.xcu = r->d_xcu;
-    a.xp2.xdec = r->d_xdec;
-    a.xp2.xtot = r->d_xtot;
-    a.xp2.dflag = r->d_dflag;
-  // the commit the round carries: the slot of the launch before this one (launch_seq not yet advanced)
-  a.xp2.csnap = e->st.csnap + (size_t)(e->launch_seq & 1ull) * e->cfg.num_partitions;
-    a.xp2.dirty = e->st.cdirty;
-    a.xp2.rowv = x.rowv;
-    a.xp2.xc = x.xc;
-    a.xp2.xc_n = x.xc_n;
-    a.xp2.counters = r->d_counters + 4;
-    a.xp2.dcap = r->dcap;
-  }
+  if (s2) a.xp2 = xplan_args(e, r->sets[s2->set]);
   if (s3) {
     XchgSet& x = r->sets[s3->set];
     a.xe3 = x.xe;
@@ -526,7 +495,7 @@ int repl_before_launch(rmq_engine* e, PipeArgs& a) {
   const uint32_t s = r->acking.front();
   if (r->sets[s].applied_launch + 3 > e->launch_seq + 1) return RMQ_OK;
   HIP_TRY(hipStreamWaitEvent(e->main_s, r->sets[s].ev_x, 0));
-  if (!r->xo_p.empty()) {
+  if (!r->lists.xo_p.empty()) {
     a.ackin = r->sets[s].ackin;
     a.ackrowv = r->sets[s].rowv;
     a.acks_round = r->sets[s].round;
@@ -581,36 +550,17 @@ int repl_after_launch(rmq_engine* e, const GroupFlight* s2, const GroupFlight* s
 // Collective like the rounds before it (every rank drains the same rounds).
 int post_notices(rmq_engine* e) {
   Replication* r = e->repl;
-  const uint32_t W = r->world, me = r->rank;
-  NoticeArgs a{};
-  a.st = e->st;
-  a.sets[0] = e->sets[0];
-  a.sets[1] = e->sets[1];
-  a.xo_p = r->d_xo_p;
-  a.out = r->d_nout;
-  a.xi_p = r->d_xi_p;
-  a.in = r->d_nin;
-  a.n_out = (uint32_t)r->xo_p.size();
-  a.n_in = (uint32_t)r->xi_p.size();
-  a.stamp = r->stamp;
+  const std::vector<uint32_t>& xo_start = r->lists.xo_start;
+  const NoticeArgs a = notice_args(e);
   launch_notice_fill(a, e->main_s);  // after the acks applied on the pipeline stream
   HIP_TRY(hipGetLastError());
-  for (uint32_t q = 0; q < W; ++q)  // rmq_fault_cut: these notices are lost (term 0: ignored)
-    if (((r->cut_notice >> q) & 1u) && r->xo_start[q + 1] > r->xo_start[q])
-      HIP_TRY(hipMemsetAsync(r->d_nout + 2ull * r->xo_start[q], 0, 16ull * (r->xo_start[q + 1] - r->xo_start[q]), e->main_s));
+  for (uint32_t q = 0; q < r->world; ++q)  // rmq_fault_cut: these notices are lost (term 0: ignored)
+    if (((r->cut_notice >> q) & 1u) && xo_start[q + 1] > xo_start[q])
+      HIP_TRY(hipMemsetAsync(r->d_nout + entry_span(xo_start, q).word, 0, entry_span(xo_start, q).bytes, e->main_s));
   r->cut_notice = 0;
   HIP_TRY(hipEventRecord(r->ev_notice, e->main_s));
   HIP_TRY(hipStreamWaitEvent(r->xchg_s, r->ev_notice, 0));
-  void* sb[kMaxWorld];
-  void* rb[kMaxWorld];
-  uint64_t sn[kMaxWorld], rn[kMaxWorld];
-  for (uint32_t q = 0; q < W; ++q) {
-    sn[q] = q == me ? 0 : 16ull * (r->xo_start[q + 1] - r->xo_start[q]);
-    rn[q] = q == me ? 0 : 16ull * (r->xi_start[q + 1] - r->xi_start[q]);
-    sb[q] = r->d_nout + 2ull * r->xo_start[q];
-    rb[q] = r->d_nin + 2ull * r->xi_start[q];
-  }
-  int rc = r->xport->exchange(sb, sn, rb, rn, r->xchg_s);
+  int rc = entry_swap(r, r->d_nout, xo_start, r->d_nin, r->lists.xi_start).post(r);
   if (rc) return rc;
   launch_notice_apply(a, r->xchg_s);
   HIP_TRY(hipGetLastError());
@@ -634,15 +584,8 @@ int repl_drain(rmq_engine* e) {
   while (!r->acking.empty()) {
     XchgSet& x = r->sets[r->acking.front()];
     HIP_TRY(hipStreamWaitEvent(e->main_s, x.ev_x, 0));
-    if (!r->xo_p.empty()) {
-      AckApplyArgs a{};
-      a.st = e->st;
-      a.outidx = r->d_outidx;
-      a.ackin = x.ackin;
-      a.rowv = x.rowv;
-      a.xreq = r->d_xreq;
-      a.acks_round = x.round;
-      launch_ack_apply(a, e->main_s);
+    if (!r->lists.xo_p.empty()) {
+      launch_ack_apply(ack_apply_args(e, x), e->main_s);
       HIP_TRY(hipGetLastError());
     }
     r->acking.pop_front();
